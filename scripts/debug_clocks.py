@@ -13,10 +13,6 @@ def sclk():
         return str(e)
     return "?"
 
-r = subprocess.run(["rocm-smi", "--setperfdeterminism", "2100"],
-                   capture_output=True, text=True)
-print("setperfdeterminism rc:", r.returncode, (r.stdout + r.stderr).strip()[-200:])
-
 from spark_gp_amd import _hip_ext as ext
 E = 100000
 g = torch.Generator().manual_seed(0)

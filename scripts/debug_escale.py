@@ -1,7 +1,6 @@
 import sys, time, subprocess
 sys.path.insert(0, "/root/repo")
 import torch
-subprocess.run(["rocm-smi", "--setperfdeterminism", "2100"], capture_output=True)
 from spark_gp_amd import _hip_ext as ext
 g = torch.Generator().manual_seed(0)
 Xall = torch.rand(100000, 100, 32, generator=g).cuda()

@@ -1,7 +1,6 @@
 import sys, os, time
 sys.path.insert(0, "/root/repo")
 import numpy as np, torch, subprocess
-subprocess.run(["rocm-smi", "--setperfdeterminism", "2100"], capture_output=True)
 from spark_gp_amd.kernels import ARDRBFKernel, EyeKernel, Scalar, compile_kernel
 from spark_gp_amd.ops import hip_backend
 from spark_gp_amd.models.base import group_experts

@@ -1,7 +1,6 @@
 import sys, time, subprocess
 sys.path.insert(0, "/root/repo")
 import numpy as np, torch
-subprocess.run(["rocm-smi", "--setperfdeterminism", "2100"], capture_output=True)
 from spark_gp_amd.ops import hip_backend, torch_backend
 from spark_gp_amd import GaussianProcessRegression
 from spark_gp_amd.kernels import ARDRBFKernel
