@@ -3,6 +3,11 @@
 Usage (GPU box):  python scripts/bench_syrk.py [rows] [m]
 Prints achieved bf16 TFLOP/s (counting all 3 hi/lo MFMA products) and the
 max relative error of KK against a torch fp64 reference.
+
+    python scripts/bench_syrk.py ROWS M --fused [D]
+times one whole PPA chunk both ways on the same inputs, alternating: the
+staged pair (cross_mfma_ppa + syrk_bf16_acc) against ppa_fused_acc over a
+split_k sweep (the table in profiles/PROFILES.md, round 3).
 """
 import os
 import sys
@@ -19,6 +24,68 @@ m = int(sys.argv[2]) if len(sys.argv) > 2 else 1000
 
 torch.manual_seed(0)
 dev = "cuda"
+
+
+def _fused_ab(rows, m, d):
+    """--fused [d]: the whole PPA chunk both ways on the same inputs,
+    alternating — cross_mfma_ppa + syrk_bf16_acc (the dispatch's split_k)
+    against ppa_fused_acc over a split_k sweep.  Times are per chunk."""
+    from spark_gp_amd.ops.ppa_gate import ppa_fused_split_k
+    X = torch.rand(rows, d, device=dev)
+    A = torch.rand(m, d, device=dev)
+    y = torch.rand(rows, device=dev)
+    beta = torch.rand(d, device=dev) + 0.5
+    Xs, As = (X * beta).contiguous(), (A * beta).contiguous()
+    nx, na = (Xs * Xs).sum(-1).contiguous(), (As * As).sum(-1).contiguous()
+    KK = torch.zeros(m, m, device=dev)
+    Ky = torch.zeros(m, dtype=torch.float64, device=dev)
+    ntile = (m + 255) // 256
+    tiles = ntile * (ntile + 1) // 2
+    sk_pair = max(1, min(16, round(4096 / tiles)))
+
+    def pair():
+        KcT, KlT = ext.cross_mfma_ppa(Xs, As, nx, na, 1.3, y, Ky)
+        ext.syrk_bf16_acc(KcT, KlT, KK, sk_pair)
+
+    def timed(fn, reps=5):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(reps):
+            fn()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) / reps * 1e3
+
+    print(f"fused A/B rows={rows} m={m} d={d} tiles={tiles} "
+          f"pair split_k={sk_pair} fused default split_k="
+          f"{ppa_fused_split_k(m)}")
+    if not ext.ppa_fused_supported(m, d):
+        pair()
+        print(f"  pair {min(timed(pair) for _ in range(3)):8.3f} ms   "
+              f"fused: unsupported (m, d)")
+        return
+    # every slice ends in a full tile of atomics: keep blocks <= 1024
+    sks = sorted(sk for sk in {1, 2, 4, 8, 16, 25, 32, 64,
+                               ppa_fused_split_k(m), max(1, 512 // tiles)}
+                 if sk == 1 or tiles * sk <= 1024)
+    pair()
+    for sk in sks:
+        def fused():
+            ext.ppa_fused_acc(Xs, As, nx, na, 1.3, y, Ky, KK, sk)
+        fused()
+        tp, tf = [], []
+        for _ in range(3):                # alternate
+            tp.append(timed(pair))
+            tf.append(timed(fused))
+        print(f"  split_k={sk:3d}: pair {min(tp):8.3f} ms (max "
+              f"{max(tp):8.3f})   fused {min(tf):8.3f} ms (max "
+              f"{max(tf):8.3f})   x{min(tp) / min(tf):.2f}")
+
+
+if "--fused" in sys.argv:
+    i = sys.argv.index("--fused")
+    _fused_ab(rows, m, int(sys.argv[i + 1]) if len(sys.argv) > i + 1 else 32)
+    sys.exit(0)
+
 # hi/lo split of a synthetic fp32 kernel block in (0, 1]
 V = torch.rand(rows, m, device=dev, dtype=torch.float32)
 Kc = V.to(torch.bfloat16)

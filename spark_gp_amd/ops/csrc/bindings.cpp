@@ -35,6 +35,13 @@ extern "C" hipError_t launch_cross_mfma(const float* Xs, const float* As,
                                          const float* yv, double* Ky,
                                          hipStream_t stream);
 
+extern "C" int syrk_fused_gen_dmax();
+
+extern "C" hipError_t launch_syrk_fused_gen(
+    const float* Xs, const float* As, const float* nx, const float* na,
+    float amp, const float* yv, int c, int m, int d, int split_k,
+    double* Ky, float* KK, hipStream_t stream);
+
 extern "C" hipError_t launch_colsum_gemv(const void* Kc, const float* y,
                                          int c, int m, double* Ky,
                                          hipStream_t stream);
@@ -302,6 +309,50 @@ void syrk_bf16_sync_acc(torch::Tensor KcT, c10::optional<torch::Tensor> KlT,
             "syrk_bf16_sync");
 }
 
+// Fused PPA accumulation: KK += K^T K (hi/lo bf16 products) and
+// Ky += K^T y with the K_nm windows generated inside the SYRK blocks from
+// the pre-scaled inputs (see syrk_fused_gen_kernel) — no K_nm in memory.
+bool ppa_fused_supported(int64_t m, int64_t d) {
+  if (m < 1 || d < 1 || d > syrk_fused_gen_dmax()) return false;
+  const int64_t ntile = (m + 255) / 256;
+  return ntile * (ntile + 1) / 2 <= 256;  // larger tile sets: sync kernel
+}
+
+void ppa_fused_acc(torch::Tensor Xs, torch::Tensor As, torch::Tensor nx,
+                   torch::Tensor na, double amp, torch::Tensor y,
+                   torch::Tensor Ky, torch::Tensor KK, int64_t split_k) {
+  TORCH_CHECK(Xs.is_cuda() && Xs.dtype() == torch::kFloat32 && Xs.dim() == 2);
+  TORCH_CHECK(As.is_cuda() && As.dtype() == torch::kFloat32 && As.dim() == 2);
+  TORCH_CHECK(Xs.size(1) == As.size(1));
+  const int c = Xs.size(0), m = As.size(0), d = Xs.size(1);
+  TORCH_CHECK(ppa_fused_supported(m, d),
+              "ppa_fused_acc: unsupported (m, d); query ppa_fused_supported");
+  TORCH_CHECK(nx.is_cuda() && nx.dtype() == torch::kFloat32 &&
+              nx.numel() == c);
+  TORCH_CHECK(na.is_cuda() && na.dtype() == torch::kFloat32 &&
+              na.numel() == m);
+  TORCH_CHECK(y.is_cuda() && y.dtype() == torch::kFloat32 && y.numel() == c);
+  TORCH_CHECK(Ky.is_cuda() && Ky.dtype() == torch::kFloat64 &&
+              Ky.numel() == m && Ky.is_contiguous());
+  TORCH_CHECK(KK.is_cuda() && KK.dtype() == torch::kFloat32 &&
+              KK.dim() == 2 && KK.size(0) == m && KK.size(1) == m &&
+              KK.is_contiguous());
+  TORCH_CHECK(split_k >= 1 && split_k <= 65535, "split_k out of range");
+  if (c == 0) return;
+  auto Xc = Xs.contiguous();
+  auto Ac = As.contiguous();
+  auto nxc = nx.contiguous();
+  auto nac = na.contiguous();
+  auto yc = y.contiguous();
+  check_hip(launch_syrk_fused_gen(
+                Xc.data_ptr<float>(), Ac.data_ptr<float>(),
+                nxc.data_ptr<float>(), nac.data_ptr<float>(), (float)amp,
+                yc.data_ptr<float>(), c, m, d, (int)split_k,
+                Ky.data_ptr<double>(), KK.data_ptr<float>(),
+                current_stream()),
+            "ppa_fused_acc");
+}
+
 void colsum_gemv_acc(torch::Tensor Kc, torch::Tensor y, torch::Tensor Ky) {
   TORCH_CHECK(Kc.is_cuda() && Kc.dtype() == torch::kBFloat16 && Kc.dim() == 2);
   TORCH_CHECK(y.is_cuda() && y.dtype() == torch::kFloat32);
@@ -557,6 +608,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("fused_expert_nll_supported", &fused_expert_nll_supported);
   mod.def("cross_mfma_ppa", &cross_mfma_ppa,
           "MFMA sqdist cross tile + fused K^T y (K1 plan, CDNA4)");
+  mod.def("ppa_fused_acc", &ppa_fused_acc,
+          "KK += K^T K, Ky += K^T y with K_nm generated in the SYRK (CDNA4)");
+  mod.def("ppa_fused_supported", &ppa_fused_supported);
   mod.def("cross_kernel_tile_ppa", &cross_kernel_tile_ppa,
           "transposed hi/lo tiles + fused K^T y accumulation (CDNA4)");
   mod.def("cross_kernel_tile", &cross_kernel_tile,

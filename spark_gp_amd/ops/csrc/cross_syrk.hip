@@ -10,6 +10,10 @@
 //  * cross_mfma         — the round-2 PPA fast path: sqdist via
 //    ||x'||^2 + ||a'||^2 - 2 x'.a' on f32 matrix cores, transposed hi/lo
 //    outputs only, Ky += K^T y fused into the epilogue.
+//  * syrk_fused_gen     — the round-3 PPA default (d <= 32, <= 256 tiles):
+//    syrk_bf16's tiles and products with the K_nm operand windows
+//    GENERATED in the block by cross_mfma's formula instead of staged
+//    through HBM; Ky += K^T y fused into the diagonal tiles.
 //  * syrk_bf16_sync     — k-synchronized persistent SYRK for large m
 //    (one block owns one tile; bounded best-effort pacing).
 //  * colsum_gemv        — Ky[m] += K_nm^T y (fp64 accumulation;
@@ -503,7 +507,314 @@ syrk_bf16_kernel(const bf16* __restrict__ KcT,  // [m, cpitch] hi^T
 // leaving KK fully populated.
 
 // ---------------------------------------------------------------------------
-// syrk_bf16_sync: k-SYNCHRONIZED variant for large m (round-2, TODO item 1)
+// syrk_fused_gen: the SYRK above with its operands GENERATED in the block
+// ---------------------------------------------------------------------------
+// K_nm is a pure function of a d-float row of X' and a d-float row of A',
+// so instead of staging hi/lo windows that cross_mfma_kernel wrote to HBM
+// (2 x 2 B x c x m per chunk, re-read once per tile that uses a window),
+// every block recomputes the two 32 x 256 operand windows of its k-step:
+//
+//  * tile geometry, wave layout, accumulators, the three bf16 MFMA passes
+//    and the atomic epilogue are syrk_bf16_kernel<true>'s;
+//  * where that kernel prefetches k-block kb+1 into registers around the
+//    MFMA phase of kb, this one generates it: wave w owns the 16-column
+//    groups 2w and 2w+1 of each window and both 16-row halves of the
+//    k-block, i.e. 8 fragments (4 on a diagonal tile) of
+//    mfma_f32_16x16x4_f32 over d, then cross_mfma_kernel's epilogue
+//    (q = nx + na - 2 dot clamped at 0, v = amp exp(-q), hi/lo split) in the
+//    same d order, so the values are the numbers that kernel would store;
+//  * the f32 D layout (col = lane&15, row = (lane>>4)*4 + r) hands each
+//    lane 4 consecutive k of one column: one 8-B store per operand into the
+//    k-major LDS tiles (80-B column pitch: conflict-free per half-wave),
+//    held in registers across the barrier like the old prefetch;
+//  * the two fp32 A' windows of the tile (2 x 256 x 36 floats = 72 KB) sit
+//    in LDS for the block's lifetime next to the four bf16 operand tiles
+//    (80 KB) and the X' stage (4.5 KB): 160,256 B of the 160 KB.  Holding
+//    the A' fragments in registers instead was tried first and spilled
+//    (143 VGPRs of scratch next to the 128 accumulators).  Both fp32 images
+//    are stored fragment-major (slot kgrp*8 + kc holds d-index kgrp + 4*kc),
+//    so a lane fetches 4 consecutive kc with one conflict-free b128 read
+//    while the MFMAs still run over d in cross_mfma_kernel's order;
+//  * X', nx and y of one k-step (32 x 34 floats) are staged through LDS,
+//    prefetched one step ahead in registers — the only global reads in
+//    the loop;
+//  * rows >= c and columns >= m generate exact zeros in hi and lo;
+//  * diagonal tiles generate one window, multiply it against itself, and
+//    are the only blocks that accumulate Ky += K^T y for their window: from
+//    the fp32 values before the split, folded into fp64 registers every
+//    k-step, one fp64 atomic per column per block;
+//  * the grid holds the upper-triangle tiles only; blocks are independent.
+//
+// d <= SF_DMAX: the LDS budget above has room for 32 d-slots per row.
+// Resources on gfx950 (hipcc -O3, -Rpass-analysis=kernel-resource-usage):
+// 234 VGPRs, 0 AGPRs, 0 B scratch, no spills, 160,256 B LDS,
+// 2 waves/SIMD (one 8-wave block per CU).
+
+#define SF_DMAX 32
+#define SF_XSTR 36    // X' staging pitch in floats: 32 d-slots, nx, y, pad;
+                      // 36*l16 mod 64 is a permutation of 4-bank blocks, so
+                      // the A-fragment reads (l16 rows x 4 k) are conflict-free
+
+template <bool DIAG>
+__device__ __forceinline__ void
+sf_tile(const float* __restrict__ Xs, const float* __restrict__ As,
+        const float* __restrict__ nx, const float* __restrict__ na,
+        const float amp, const float* __restrict__ yv,
+        const int c, const int m, const int d, const int i0, const int j0,
+        const int kb0, const int kb1,
+        bf16* __restrict__ lt, bf16* __restrict__ rt,
+        bf16* __restrict__ ltl, bf16* __restrict__ rtl,
+        float* __restrict__ xs, float* __restrict__ aw,
+        double* __restrict__ Ky, float* __restrict__ KK) {
+  constexpr int NG = DIAG ? 2 : 4;        // generated column groups per wave
+  const int tid = threadIdx.x;
+  const int wave = tid >> 6;              // 0..7
+  const int lane = tid & 63;
+  const int wr = (wave >> 1) * 64;        // wave row offset in tile
+  const int wc = (wave & 1) * 128;        // wave col offset in tile
+  const int l16 = lane & 15;
+  const int kgrp = lane >> 4;
+  const int crow = kgrp * 4;              // f32 D fragment: first row of 4
+
+  f32x4 acc[4][8];
+#pragma unroll
+  for (int a = 0; a < 4; ++a)
+#pragma unroll
+    for (int b = 0; b < 8; ++b) acc[a][b] = {0.f, 0.f, 0.f, 0.f};
+
+  // generation role: group g -> window g>>1 (0 = rows i0.., 1 = cols j0..),
+  // 16-column group 2*wave + (g&1) of that window; lane's column = l16
+  float nav[NG];
+  bool cok[NG];
+#pragma unroll
+  for (int g = 0; g < NG; ++g) {
+    const int gc = ((g >> 1) ? j0 : i0) + (wave * 2 + (g & 1)) * 16 + l16;
+    cok[g] = gc < m;
+    nav[g] = cok[g] ? na[gc] : 0.f;
+  }
+
+  // A' windows -> LDS once per block, fragment-major: slot kgrp*8 + kc holds
+  // d-index kgrp + 4*kc, so a lane's 4 consecutive kc are one b128 read.
+  // Columns >= m and d-slots >= d are zeros.
+  for (int f = tid; f < (DIAG ? 1 : 2) * SY_CT * SF_DMAX; f += SY_WG) {
+    const int w = f / (SY_CT * SF_DMAX);
+    const int col = (f / SF_DMAX) % SY_CT, q = f % SF_DMAX;
+    const int gc = (w ? j0 : i0) + col;
+    aw[(w * SY_CT + col) * SF_XSTR + (q & 3) * 8 + (q >> 2)] =
+        (gc < m && q < d) ? As[(size_t)gc * d + q] : 0.f;
+  }
+
+  // X' staging (same fragment-major slots, + nx at 32, y at 33): thread ->
+  // (row, d-slots xsl and xsl+16); lanes 0/1 of each 16 also carry the
+  // row's nx / y.  Rows >= c stage zeros.
+  const int xrow = tid >> 4, xsl = tid & 15;
+  float px0, px1, pe;
+  auto gload = [&](int kb) {
+    const int gr = kb * SY_BK + xrow;
+    const bool ok = gr < c;
+    px0 = (ok && xsl < d) ? Xs[(size_t)gr * d + xsl] : 0.f;
+    px1 = (ok && xsl + 16 < d) ? Xs[(size_t)gr * d + xsl + 16] : 0.f;
+    pe = 0.f;
+    if (ok && xsl == 0) pe = nx[gr];
+    if (ok && xsl == 1) pe = yv[gr];
+  };
+  auto xwrite = [&]() {
+    const int o = xrow * SF_XSTR + (xsl & 3) * 8 + (xsl >> 2);
+    xs[o] = px0;
+    xs[o + 4] = px1;                      // d-slot xsl + 16 -> kc + 4
+    if (xsl < 2) xs[xrow * SF_XSTR + 32 + xsl] = pe;
+  };
+
+  uint2 gh[2][NG], gl[2][NG];             // generated hi/lo, 4 k per lane
+  double kyacc[NG] = {0.0};               // DIAG only: Ky partial per group
+  auto generate = [&](int kb) {
+    f32x4 dacc[2][NG];
+#pragma unroll
+    for (int rg = 0; rg < 2; ++rg)
+#pragma unroll
+      for (int g = 0; g < NG; ++g) dacc[rg][g] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {         // kc = 4h .. 4h+3, in d order
+      if (h * 16 < d) {                   // uniform; skipped slots are 0*0
+        f32x4 xa[2], ab[NG];
+#pragma unroll
+        for (int rg = 0; rg < 2; ++rg)
+          xa[rg] = *(const f32x4*)&xs[(rg * 16 + l16) * SF_XSTR + kgrp * 8 +
+                                      h * 4];
+#pragma unroll
+        for (int g = 0; g < NG; ++g)
+          ab[g] = *(const f32x4*)&aw[((g >> 1) * SY_CT +
+                                      (wave * 2 + (g & 1)) * 16 + l16) *
+                                         SF_XSTR + kgrp * 8 + h * 4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+#pragma unroll
+          for (int rg = 0; rg < 2; ++rg)
+#pragma unroll
+            for (int g = 0; g < NG; ++g)
+              dacc[rg][g] = __builtin_amdgcn_mfma_f32_16x16x4f32(
+                  xa[rg][u], ab[g][u], dacc[rg][g], 0, 0, 0);
+      }
+      // keep the second half's fragment loads out of the first half's
+      // live range (register budget)
+      __builtin_amdgcn_sched_barrier(0);
+    }
+#pragma unroll
+    for (int rg = 0; rg < 2; ++rg) {
+      const int lr0 = rg * 16 + crow;
+      const int gr0 = kb * SY_BK + lr0;
+      float nxr[4], yr[4];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        nxr[r] = xs[(lr0 + r) * SF_XSTR + 32];
+        if (DIAG) yr[r] = xs[(lr0 + r) * SF_XSTR + 33];
+      }
+#pragma unroll
+      for (int g = 0; g < NG; ++g) {
+        bf16 th[4], tl[4];
+        float kysum = 0.f;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const float q = nxr[r] + nav[g] - 2.0f * dacc[rg][g][r];
+          float v = amp * __expf(-(q > 0.f ? q : 0.f));
+          v = (cok[g] && gr0 + r < c) ? v : 0.f;   // exact zeros outside
+          if (DIAG) kysum += v * yr[r];            // y stages 0 for rows >= c
+          const bf16 h = (bf16)v;
+          th[r] = h;
+          tl[r] = (bf16)(v - (float)h);
+        }
+        gh[rg][g] = *(uint2*)th;
+        gl[rg][g] = *(uint2*)tl;
+        if (DIAG) kyacc[g] += (double)kysum;
+      }
+    }
+  };
+  auto write_gen = [&]() {
+#pragma unroll
+    for (int rg = 0; rg < 2; ++rg)
+#pragma unroll
+      for (int g = 0; g < NG; ++g) {
+        const int lc = (wave * 2 + (g & 1)) * 16 + l16;
+        const int o = lc * SY_STR + rg * 16 + crow;
+        *(uint2*)&((g >> 1) ? rt : lt)[o] = gh[rg][g];
+        *(uint2*)&((g >> 1) ? rtl : ltl)[o] = gl[rg][g];
+      }
+  };
+  auto mfma_pass = [&](const bf16* at, const bf16* bt) {
+    bf16x8 fa[4], fb[4];
+    const int ko = kgrp * 8;
+#pragma unroll
+    for (int a = 0; a < 4; ++a)
+      fa[a] = *(const bf16x8*)&at[(wr + a * 16 + l16) * SY_STR + ko];
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+#pragma unroll
+      for (int b = 0; b < 4; ++b)
+        fb[b] = *(const bf16x8*)&bt[(wc + (h * 4 + b) * 16 + l16) * SY_STR
+                                    + ko];
+#pragma unroll
+      for (int a = 0; a < 4; ++a)
+#pragma unroll
+        for (int b = 0; b < 4; ++b)
+          acc[a][h * 4 + b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+              fa[a], fb[b], acc[a][h * 4 + b], 0, 0, 0);
+    }
+  };
+
+  gload(kb0);
+  xwrite();
+  __syncthreads();
+  if (kb0 + 1 < kb1) gload(kb0 + 1);
+  generate(kb0);
+  for (int kb = kb0; kb < kb1; ++kb) {
+    const bool more = kb + 1 < kb1;       // block-uniform
+    __syncthreads();                      // xs and the tiles are free
+    write_gen();                          // operands of block kb
+    if (more) xwrite();                   // X' of block kb+1
+    __syncthreads();
+    if (more && kb + 2 < kb1) gload(kb + 2);   // covered by a whole step
+    // Generation of kb+1 and the products of kb are independent, but they
+    // share the matrix pipe, and their transient registers (X'/A'
+    // fragments + f32 tiles vs. bf16 fragments) must not be live together:
+    // the sched barriers keep the phases apart (234 VGPRs, no scratch;
+    // without them the allocator spills).  Running the two phases in
+    // opposite order on the two waves of a SIMD was measured: no gain.
+    if (more) generate(kb + 1);
+    __builtin_amdgcn_sched_barrier(0);
+    mfma_pass(lt, DIAG ? lt : rt);        // hi * hi
+    __builtin_amdgcn_sched_barrier(0);
+    mfma_pass(lt, DIAG ? ltl : rtl);      // hi * lo
+    __builtin_amdgcn_sched_barrier(0);
+    mfma_pass(ltl, DIAG ? lt : rt);       // lo * hi
+  }
+
+  // epilogue: C/D layout for 16x16x32: col = lane&15, row = (lane>>4)*4 + r
+#pragma unroll
+  for (int a = 0; a < 4; ++a)
+#pragma unroll
+    for (int b = 0; b < 8; ++b)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int gi = i0 + wr + a * 16 + crow + r;
+        const int gj = j0 + wc + b * 16 + l16;
+        if (gi < m && gj < m) {
+          atomicAdd(&KK[(size_t)gi * m + gj], acc[a][b][r]);
+          if (!DIAG)             // mirror off-diagonal tiles
+            atomicAdd(&KK[(size_t)gj * m + gi], acc[a][b][r]);
+        }
+      }
+
+  if (DIAG) {
+    // the 4 k-groups of a wave hold partials of the same 16 columns
+#pragma unroll
+    for (int g = 0; g < 2; ++g) {
+      double t = kyacc[g];
+      t += __shfl_xor(t, 16);
+      t += __shfl_xor(t, 32);
+      const int gc = i0 + (wave * 2 + g) * 16 + l16;
+      if (kgrp == 0 && gc < m) atomicAdd(&Ky[gc], t);
+    }
+  }
+}
+
+__global__ void __launch_bounds__(SY_WG, 2)
+syrk_fused_gen_kernel(const float* __restrict__ Xs,   // [c, d] pre-scaled
+                      const float* __restrict__ As,   // [m, d] pre-scaled
+                      const float* __restrict__ nx,   // [c] ||x'||^2
+                      const float* __restrict__ na,   // [m] ||a'||^2
+                      const float amp,
+                      const float* __restrict__ yv,   // [c]
+                      const int c, const int m, const int d, const int ntile,
+                      const int split_k,
+                      double* __restrict__ Ky,        // [m] accumulated
+                      float* __restrict__ KK) {       // [m, m] accumulated
+  __shared__ __align__(16) bf16 lt[SY_CT * SY_STR];
+  __shared__ __align__(16) bf16 rt[SY_CT * SY_STR];
+  __shared__ __align__(16) bf16 ltl[SY_CT * SY_STR];
+  __shared__ __align__(16) bf16 rtl[SY_CT * SY_STR];
+  __shared__ __align__(16) float xs[SY_BK * SF_XSTR];
+  __shared__ __align__(16) float aw[2 * SY_CT * SF_XSTR];
+
+  // blockIdx.x enumerates the upper triangle row by row
+  int ti = 0, rem = blockIdx.x;
+  while (rem >= ntile - ti) { rem -= ntile - ti; ++ti; }
+  const int tj = ti + rem;
+  const int kblocks = (c + SY_BK - 1) / SY_BK;
+  const int per = (kblocks + split_k - 1) / split_k;
+  const int kb0 = blockIdx.y * per;
+  const int kb1 = min(kblocks, kb0 + per);
+  if (kb0 >= kb1) return;                 // empty slice (block-uniform)
+
+  if (ti == tj)
+    sf_tile<true>(Xs, As, nx, na, amp, yv, c, m, d, ti * SY_CT, tj * SY_CT,
+                  kb0, kb1, lt, rt, ltl, rtl, xs, aw, Ky, KK);
+  else
+    sf_tile<false>(Xs, As, nx, na, amp, yv, c, m, d, ti * SY_CT, tj * SY_CT,
+                   kb0, kb1, lt, rt, ltl, rtl, xs, aw, Ky, KK);
+}
+
+// ---------------------------------------------------------------------------
+// syrk_bf16_sync:k-SYNCHRONIZED variant for large m (round-2, TODO item 1)
 // ---------------------------------------------------------------------------
 // At m >= 4096 the plain kernel's co-scheduled tiles drift apart in k, so
 // no XCD's L2 ever holds the column windows its tiles are reading (round-1
@@ -756,6 +1067,20 @@ extern "C" hipError_t launch_syrk_bf16(const void* KcT, const void* KlT,
                        stream, (const bf16*)KcT, nullptr, c, m, cpitch,
                        ntile, split_k, KK);
   }
+  return hipGetLastError();
+}
+
+extern "C" int syrk_fused_gen_dmax() { return SF_DMAX; }
+
+extern "C" hipError_t launch_syrk_fused_gen(
+    const float* Xs, const float* As, const float* nx, const float* na,
+    float amp, const float* yv, int c, int m, int d, int split_k,
+    double* Ky, float* KK, hipStream_t stream) {
+  const int ntile = (m + SY_CT - 1) / SY_CT;
+  dim3 grid(ntile * (ntile + 1) / 2, split_k);   // upper-triangle tiles
+  hipLaunchKernelGGL(syrk_fused_gen_kernel, grid, dim3(SY_WG), 0, stream,
+                     Xs, As, nx, na, amp, yv, c, m, d, ntile, split_k, Ky,
+                     KK);
   return hipGetLastError();
 }
 

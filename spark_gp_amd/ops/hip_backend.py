@@ -18,6 +18,8 @@ from ..kernels.base import Kernel
 from ..kernels.compiled import CompiledKernel, compile_kernel
 from .. import _hip_ext as ext
 from . import torch_backend
+from .ppa_gate import (ppa_fused_chunk_rows, ppa_fused_gate,
+                       ppa_fused_split_k)
 
 
 def _scale_vector(cs: CompiledKernel, theta: np.ndarray, d: int,
@@ -294,17 +296,31 @@ def kmn_knm_and_kmny(kernel: Kernel, active: torch.Tensor,
     # transposed hi/lo copies the SYRK stages from and accumulating
     # Ky += K^T y in the same launch.  The elementwise kernel (~3 VALU
     # issues per (element, dim)) remains as the fallback/AB path.
+    #
+    # Fused path (default where the gate allows): the SYRK blocks generate
+    # their K_nm operand windows themselves from the same pre-scaled inputs
+    # and formula, so no [m, chunk] hi/lo buffers are written or re-read
+    # (SPARK_GP_AMD_PPA_FUSED=0 selects the two-kernel path for A/B).
     import os
     use_mfma = os.environ.get("SPARK_GP_AMD_CROSS_MFMA", "1") == "1"
+    use_fused = (use_mfma and ppa_fused_gate(m, d, X.dtype)
+                 and bool(ext.ppa_fused_supported(m, d)))
     if use_mfma:
         svec = _scale_vector(cs, theta, d, X.device)
         As = (act32 * svec).contiguous()
         na = (As * As).sum(-1).contiguous()
+    if use_fused:
+        chunk_rows = ppa_fused_chunk_rows(chunk_rows)
     for s in range(0, n, chunk_rows):
         e = min(n, s + chunk_rows)
         if use_mfma:
             Xs = (X[s:e] * svec).contiguous()
             nx = (Xs * Xs).sum(-1).contiguous()
+            if use_fused:
+                ext.ppa_fused_acc(Xs, As, nx, na, float(C),
+                                  y32[s:e].contiguous(), Ky, KK,
+                                  ppa_fused_split_k(m))
+                continue
             KcT, KlT = ext.cross_mfma_ppa(Xs, As, nx, na, float(C),
                                           y32[s:e].contiguous(), Ky)
         else:
