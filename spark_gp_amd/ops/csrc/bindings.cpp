@@ -6,6 +6,8 @@
 
 #include <vector>
 
+#include "kernel_geom.h"
+
 extern "C" hipError_t launch_fused_expert_nll(
     const float* X, const float* y, const float* scale, float amp,
     float noise, int E, int k, int d, double* out_nll, double* out_sumW0,
@@ -34,8 +36,6 @@ extern "C" hipError_t launch_cross_mfma(const float* Xs, const float* As,
                                          void* out_bfT, void* out_loT,
                                          const float* yv, double* Ky,
                                          hipStream_t stream);
-
-extern "C" int syrk_fused_gen_dmax();
 
 extern "C" hipError_t launch_syrk_fused_gen(
     const float* Xs, const float* As, const float* nx, const float* na,
@@ -135,22 +135,9 @@ std::vector<torch::Tensor> fused_expert_nll(torch::Tensor X, torch::Tensor y,
   return fused_expert_nll_impl(X, y, scale, amp, noise, false);
 }
 
-namespace {
-inline int64_t a16i(int64_t n) { return (n + 15) & ~(int64_t)15; }
-inline int64_t sa_of(int64_t k) { return (k + 4) & ~(int64_t)3; }
-inline int64_t tsz_of(int64_t k) {
-  return std::max<int64_t>(std::max<int64_t>(k * 36, 32 * sa_of(k)), 448);
-}
-}  // namespace
-
 bool fused_expert_nll_supported(int64_t k, int64_t d) {
   if (k > 128 || d > 128 || k < 1) return false;
-  // LDS budget: EXACT mirror of nll_lds_bytes2 in expert_nll.hip
-  const int64_t dp4 = (d + 4) & ~(int64_t)3;
-  int64_t bytes = a16i(8 * 10) + a16i(4 * k * sa_of(k)) +
-                  a16i(4 * tsz_of(k)) + a16i(4 * k * dp4) +
-                  4 * a16i(4 * k) + a16i(4 * d) + 16;
-  return bytes <= 160 * 1024;
+  return nll_lds_bytes((int)k, (int)d) <= GEOM_LDS_MAX;
 }
 
 std::vector<torch::Tensor> cross_kernel_tile(torch::Tensor X, torch::Tensor A,
@@ -296,7 +283,7 @@ void syrk_bf16_sync_acc(torch::Tensor KcT, c10::optional<torch::Tensor> KlT,
                 KlT->dtype() == torch::kBFloat16);
     Klc = KlT->contiguous();
   }
-  const int kblocks = (c + 31) / 32;
+  const int kblocks = (c + SY_BK - 1) / SY_BK;
   const int nphases = (kblocks + (int)kpb - 1) / (int)kpb;
   auto ctr = torch::zeros({nphases},
                           torch::TensorOptions().dtype(torch::kInt32)
@@ -313,8 +300,8 @@ void syrk_bf16_sync_acc(torch::Tensor KcT, c10::optional<torch::Tensor> KlT,
 // Ky += K^T y with the K_nm windows generated inside the SYRK blocks from
 // the pre-scaled inputs (see syrk_fused_gen_kernel) — no K_nm in memory.
 bool ppa_fused_supported(int64_t m, int64_t d) {
-  if (m < 1 || d < 1 || d > syrk_fused_gen_dmax()) return false;
-  const int64_t ntile = (m + 255) / 256;
+  if (m < 1 || d < 1 || d > SF_DMAX) return false;
+  const int64_t ntile = (m + SY_CT - 1) / SY_CT;
   return ntile * (ntile + 1) / 2 <= 256;  // larger tile sets: sync kernel
 }
 
@@ -404,12 +391,7 @@ std::vector<torch::Tensor> fused_laplace_newton(torch::Tensor X,
 
 bool fused_laplace_newton_supported(int64_t k, int64_t d) {
   if (k > 128 || d > k || k < 1) return false;
-  // EXACT mirror of lap_lds_bytes in laplace.hip (single-buffer design)
-  const int64_t dp4 = (d + 4) & ~(int64_t)3;
-  int64_t bytes = a16i(8 * 10) + a16i(4 * k * sa_of(k)) +
-                  a16i(4 * k * dp4) +
-                  a16i(4 * tsz_of(k)) + 8 * a16i(4 * k) + a16i(4 * d) + 16;
-  return bytes <= 160 * 1024;
+  return lap_lds_bytes((int)k, (int)d) <= GEOM_LDS_MAX;
 }
 
 // Fused Newton + Algorithm 5.1 evidence/gradient (K11).  Runs the Newton
@@ -455,13 +437,7 @@ std::vector<torch::Tensor> fused_laplace_evidence(torch::Tensor X,
 
 bool fused_laplace_evidence_supported(int64_t k, int64_t d) {
   if (k > 128 || d > k || k < 1) return false;
-  // EXACT mirror of lap_lds_bytes(k, d, ev=1) in laplace.hip
-  const int64_t dp4 = (d + 4) & ~(int64_t)3;
-  int64_t bytes = a16i(8 * 10) + a16i(4 * k * sa_of(k)) +
-                  a16i(4 * k * dp4) +
-                  a16i(4 * tsz_of(k)) + 8 * a16i(4 * k) + a16i(4 * d) + 16 +
-                  2 * a16i(4 * k) + a16i(4 * d) + a16i(8 * (d + 2));
-  return bytes <= 160 * 1024;
+  return lap_lds_bytes((int)k, (int)d, 1) <= GEOM_LDS_MAX;
 }
 
 // ---------------------------------------------------------------------------

@@ -20,6 +20,15 @@
 //    superseded on the PPA path by the fused epilogues, kept as the
 //    standalone op).
 //
+// The three SYRK kernels are one tile body with three fronts.  Defined once
+// and shared: the bf16 product pass (syrk_mfma_pass), the tile epilogue
+// (syrk_epilogue, atomic or plain), the k-slice range (syrk_kslice), and for
+// the two kernels that stage operands from HBM the lane decomposition,
+// the load / LDS-write / prefetch pipeline and its k-loop
+// (syrk_staged_steps).  The K_nm value formula (knm_value) and the hi/lo
+// split (split_hilo) are shared by the kernel that stores K_nm and the one
+// that generates it.  Tile constants shared with the host: kernel_geom.h.
+//
 // Replaces ProjectedGaussianProcessHelper.scala:20-36's per-expert
 // crossKernel + breeze gemm accumulation.
 
@@ -27,9 +36,27 @@
 #include <hip/hip_bf16.h>
 #include <math.h>
 
+#include "kernel_geom.h"    // SY_CT, SY_BK, SF_DMAX (shared with the host)
+
 typedef __bf16 bf16;
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
+
+// K_nm from pre-scaled inputs: q = ||x'||^2 + ||a'||^2 - 2 x'.a' clamped at
+// 0, v = amp exp(-q).  cross_mfma_kernel stores these values and
+// syrk_fused_gen_kernel generates them; both call this one definition.
+__device__ __forceinline__ float knm_value(const float nx, const float na,
+                                           const float dot, const float amp) {
+  const float q = nx + na - 2.0f * dot;
+  return amp * __expf(-(q > 0.f ? q : 0.f));
+}
+
+// hi/lo split: hi + lo carries ~16 mantissa bits, so the SYRK's
+// input-quantization error drops to fp32 class
+__device__ __forceinline__ void split_hilo(const float v, bf16& hi, bf16& lo) {
+  hi = (bf16)v;
+  lo = (bf16)(v - (float)hi);
+}
 
 // ---------------------------------------------------------------------------
 // cross_kernel_tile: 128x128 output tile per 256-thread block, d-chunked LDS
@@ -102,8 +129,7 @@ cross_kernel_tile_kernel(const float* __restrict__ X,    // [c, d]
     __syncthreads();
   }
 
-  // finalize the 8x8 micro-tile once; hi/lo split: hi + lo carries ~16
-  // mantissa bits, so the SYRK's input-quantization error drops to fp32 class
+  // finalize the 8x8 micro-tile once
   bf16 hv[8][8], lv[8][8];
 #pragma unroll
   for (int i = 0; i < 8; ++i)
@@ -111,8 +137,7 @@ cross_kernel_tile_kernel(const float* __restrict__ X,    // [c, d]
     for (int j = 0; j < 8; ++j) {
       const float v = amp * __expf(-acc[i][j]);
       acc[i][j] = v;
-      hv[i][j] = (bf16)v;
-      lv[i][j] = (bf16)(v - (float)hv[i][j]);
+      split_hilo(v, hv[i][j], lv[i][j]);
     }
 
 #pragma unroll
@@ -294,13 +319,10 @@ cross_mfma_kernel(const float* __restrict__ Xs,   // [c, d] pre-scaled
         const int gr = gr0 + r;
         float v = 0.f;
         if (gr < c) {
-          const float q = nx[gr] + nav - 2.0f * acc[a][b][r];
-          v = amp * __expf(-(q > 0.f ? q : 0.f));
+          v = knm_value(nx[gr], nav, acc[a][b][r], amp);
           kysum += v * yv[gr];
         }
-        const bf16 h = (bf16)v;
-        th[r] = h;
-        tl[r] = (bf16)(v - (float)h);
+        split_hilo(v, th[r], tl[r]);
       }
       if ((c % 4 == 0) && gr0 + 4 <= c) {   // 8-B alignment needs 4 | c
         *(uint2*)&out_bfT[(size_t)gc * c + gr0] = *(uint2*)th;
@@ -325,17 +347,17 @@ cross_mfma_kernel(const float* __restrict__ Xs,   // [c, d] pre-scaled
 }
 
 // ---------------------------------------------------------------------------
-// syrk_bf16: KK[m, m] += K^T K from the TRANSPOSED chunk KcT [m, c]
+// The SYRK tile body shared by syrk_bf16, syrk_fused_gen and syrk_bf16_sync
 // ---------------------------------------------------------------------------
 // 512-thread block = 8 waves in a 4x2 grid; 256x256 output tile per block
 // (the largest tile the LDS+register budget allows: per-CU VMEM return
 // throughput (~10 B/cyc/CU HBM-bound) is the wall, and bytes/flop scales
 // as (M+N)/(M*N), so 256^2 halves traffic vs 128^2); each wave computes a
-// 64x128 sub-tile as 4x8 mfma_f32_16x16x32_bf16 tiles.  K-loop: BK=32
-// rows staged k-major in LDS; split-K over the chunk rows for occupancy.
+// 64x128 sub-tile as 4x8 mfma_f32_16x16x32_bf16 tiles.  K-loop: SY_BK=32
+// rows held k-major in LDS.  The three kernels differ in where the operand
+// tiles come from (staged from HBM or generated), in how blocks are paced,
+// and in atomic vs plain accumulation; everything below is common.
 
-#define SY_BK 32
-#define SY_CT 256     // output tile edge (per block)
 #define SY_WG 512
 #define SY_STR 40     // k-major [SY_CT][SY_STR] bf16: 32 k + 8 pad = 80-B
                       // rows.  80 B x 16 consecutive lanes covers all 64
@@ -344,6 +366,241 @@ cross_mfma_kernel(const float* __restrict__ Xs,   // [c, d] pre-scaled
                       // b128 reads are both conflict-free.  4 operands x
                       // 20 KB = 80 KB -> one 8-wave block/CU (2 waves/SIMD).
 
+typedef f32x4 SyAcc[4][8];                // a wave's 64x128 fp32 sub-tile
+
+struct SyLane {
+  int tid, wave, lane;
+  int wr, wc;                             // wave row / col offset in tile
+  int l16;                                // fragment row/col
+  int kgrp;                               // 0..3 -> k-subblock of 8
+};
+
+__device__ __forceinline__ SyLane sy_lane() {
+  SyLane L;
+  L.tid = threadIdx.x;
+  L.wave = L.tid >> 6;                    // 0..7
+  L.lane = L.tid & 63;
+  L.wr = (L.wave >> 1) * 64;
+  L.wc = (L.wave & 1) * 128;
+  L.l16 = L.lane & 15;
+  L.kgrp = L.lane >> 4;
+  return L;
+}
+
+__device__ __forceinline__ void sy_zero(SyAcc& acc) {
+#pragma unroll
+  for (int a = 0; a < 4; ++a)
+#pragma unroll
+    for (int b = 0; b < 8; ++b) acc[a][b] = {0.f, 0.f, 0.f, 0.f};
+}
+
+// the four k-major bf16 operand tiles of one k-block: rows i0.. (lt) and
+// j0.. (rt) of hi^T, and the same of lo^T (ltl, rtl; unused without HILO)
+struct SyTiles {
+  bf16 *lt, *rt, *ltl, *rtl;
+};
+
+__device__ __forceinline__ int syrk_kblocks(const int c) {
+  return (c + SY_BK - 1) / SY_BK;
+}
+
+// k-blocks [kb0, kb1) of slice `slice` out of split_k; false when empty
+__device__ __forceinline__ bool syrk_kslice(const int c, const int split_k,
+                                            const int slice, int& kb0,
+                                            int& kb1) {
+  const int kblocks = syrk_kblocks(c);
+  const int per = (kblocks + split_k - 1) / split_k;
+  kb0 = slice * per;
+  kb1 = min(kblocks, kb0 + per);
+  return kb0 < kb1;
+}
+
+// one bf16 product pass acc += at^T bt over a k-block, in two b-halves of
+// 16 INDEPENDENT MFMAs (no accumulator chaining between consecutive
+// issues); fb covers 4 of the 8 column tiles at a time to stay inside the
+// register budget.  (This and syrk_epilogue take the lane's offsets as four
+// ints, not as a SyLane: syrk_fused_gen calls them too, see its note.)
+__device__ __forceinline__ void syrk_mfma_pass(SyAcc& acc, const bf16* at,
+                                               const bf16* bt, const int wr,
+                                               const int wc, const int l16,
+                                               const int kgrp) {
+  bf16x8 fa[4], fb[4];
+  const int ko = kgrp * 8;
+#pragma unroll
+  for (int a = 0; a < 4; ++a)
+    fa[a] = *(const bf16x8*)&at[(wr + a * 16 + l16) * SY_STR + ko];
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+#pragma unroll
+    for (int b = 0; b < 4; ++b)
+      fb[b] = *(const bf16x8*)&bt[(wc + (h * 4 + b) * 16 + l16) * SY_STR
+                                  + ko];
+#pragma unroll
+    for (int a = 0; a < 4; ++a)
+#pragma unroll
+      for (int b = 0; b < 4; ++b)
+        acc[a][h * 4 + b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+            fa[a], fb[b], acc[a][h * 4 + b], 0, 0, 0);
+  }
+}
+
+// the products of one k-block: hi^T hi, and with HILO + hi^T lo + lo^T hi
+// (lo^T lo ~ 2^-32, dropped), for the staged kernels.  syrk_fused_gen
+// issues the same three passes itself, with scheduling barriers between
+// them and the operands aliased on diagonal tiles.
+template <bool HILO>
+__device__ __forceinline__ void syrk_products(SyAcc& acc, const SyTiles& T,
+                                              const SyLane& L) {
+  syrk_mfma_pass(acc, T.lt, T.rt, L.wr, L.wc, L.l16, L.kgrp);     // hi * hi
+  if (HILO) {
+    syrk_mfma_pass(acc, T.lt, T.rtl, L.wr, L.wc, L.l16, L.kgrp);  // hi * lo
+    syrk_mfma_pass(acc, T.ltl, T.rt, L.wr, L.wc, L.l16, L.kgrp);  // lo * hi
+  }
+}
+
+// KK tile (i0, j0) += acc, plus its transpose when `mirror`.  C/D layout of
+// 16x16x32: col = lane&15, row = (lane>>4)*4 + r.  ATOMIC: several blocks
+// (k-slices) add into one element; otherwise the block is the element's
+// only owner in this launch and accumulates plainly.
+template <bool ATOMIC>
+__device__ __forceinline__ void syrk_epilogue(const SyAcc& acc,
+                                              float* __restrict__ KK,
+                                              const int m, const int i0,
+                                              const int j0, const bool mirror,
+                                              const int wr, const int wc,
+                                              const int l16, const int kgrp) {
+  const int crow = kgrp * 4;
+#pragma unroll
+  for (int a = 0; a < 4; ++a)
+#pragma unroll
+    for (int b = 0; b < 8; ++b)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int gi = i0 + wr + a * 16 + crow + r;
+        const int gj = j0 + wc + b * 16 + l16;
+        if (gi < m && gj < m) {
+          if (ATOMIC) {
+            atomicAdd(&KK[(size_t)gi * m + gj], acc[a][b][r]);
+            if (mirror) atomicAdd(&KK[(size_t)gj * m + gi], acc[a][b][r]);
+          } else {
+            KK[(size_t)gi * m + gj] += acc[a][b][r];
+            if (mirror) KK[(size_t)gj * m + gi] += acc[a][b][r];
+          }
+        }
+      }
+}
+
+// ---------------------------------------------------------------------------
+// Staged operands: the TRANSPOSED chunk KcT [m, c] (and KlT) read from HBM
+// ---------------------------------------------------------------------------
+// Operands arrive TRANSPOSED ([m, c], written for free by the cross
+// kernel's register tile), so k runs along the contiguous axis: staging
+// is one uint4 global load (8 lanes = one full 128-B line) + one
+// conflict-free b128 LDS write per thread, and every MFMA fragment is
+// one b128 LDS read.  The old [c, m]-operand versions were LDS- or
+// VMEM-instruction bound (8 scalar ops per fragment either way).
+//
+// thread -> (column, 8-deep k segment); 256 cols x 4 segs = 1024 slots per
+// operand = 2 iterations of 512 threads.  Adjacent 4 lanes take the 4
+// k-segments of one column (64-B half-lines; the other half of each 128-B
+// line is the next k-block's data and hits L2).
+
+struct SyOperands {
+  const bf16* KcT;                        // [m, cpitch] hi^T
+  const bf16* KlT;                        // [m, cpitch] lo^T (HILO)
+  int c, m, cpitch;
+};
+
+typedef uint4 SyPrefetch[2][4];           // [iteration][operand]
+
+// 8 consecutive k of column gc; zeros for gc >= m and k >= c
+__device__ __forceinline__ uint4 syrk_load8(const bf16* mat,
+                                            const SyOperands& P,
+                                            const int gc, const int gk0) {
+  uint4 v;
+  bf16* vals = (bf16*)&v;
+  const bool vec_ok = (P.cpitch % 8 == 0);   // 16-B aligned row starts
+  if (gc < P.m && vec_ok && gk0 + 8 <= P.c) {
+    v = *(const uint4*)(mat + (size_t)gc * P.cpitch + gk0);
+  } else if (gc < P.m) {
+#pragma unroll
+    for (int u = 0; u < 8; ++u)
+      vals[u] = (gk0 + u < P.c) ? mat[(size_t)gc * P.cpitch + gk0 + u]
+                                : (bf16)0.f;
+  } else {
+#pragma unroll
+    for (int u = 0; u < 8; ++u) vals[u] = (bf16)0.f;
+  }
+  return v;
+}
+
+template <bool HILO>
+__device__ __forceinline__ void syrk_stage_load(SyPrefetch& sv,
+                                                const SyOperands& P,
+                                                const int i0, const int j0,
+                                                const int kb, const int tid) {
+#pragma unroll
+  for (int it = 0; it < 2; ++it) {
+    const int f = tid + it * SY_WG;       // 0..1023
+    const int col = f >> 2;
+    const int gk0 = kb * SY_BK + (f & 3) * 8;
+    sv[it][0] = syrk_load8(P.KcT, P, i0 + col, gk0);
+    sv[it][1] = syrk_load8(P.KcT, P, j0 + col, gk0);
+    if (HILO) {
+      sv[it][2] = syrk_load8(P.KlT, P, i0 + col, gk0);
+      sv[it][3] = syrk_load8(P.KlT, P, j0 + col, gk0);
+    }
+  }
+}
+
+template <bool HILO>
+__device__ __forceinline__ void syrk_stage_write(const SyPrefetch& sv,
+                                                 const SyTiles& T,
+                                                 const int tid) {
+#pragma unroll
+  for (int it = 0; it < 2; ++it) {
+    const int f = tid + it * SY_WG;
+    const int o = (f >> 2) * SY_STR + (f & 3) * 8;
+    *(uint4*)&T.lt[o] = sv[it][0];
+    *(uint4*)&T.rt[o] = sv[it][1];
+    if (HILO) {
+      *(uint4*)&T.ltl[o] = sv[it][2];
+      *(uint4*)&T.rtl[o] = sv[it][3];
+    }
+  }
+}
+
+// k-blocks [kb0, kb1) of tile (i0, j0), with block kb0 already in sv.
+// Single-buffer T14 register pipeline: the loads for block kb+1 (while
+// kb + 1 < kb_end) are issued before the MFMA phase of block kb, which
+// covers their latency; the per-CU VMEM return rate (~10 B/cyc HBM-bound)
+// is the wall, which is why the tile is as large as LDS allows.
+template <bool HILO>
+__device__ __forceinline__ void syrk_staged_steps(
+    SyAcc& acc, SyPrefetch& sv, const SyOperands& P, const int i0,
+    const int j0, const int kb0, const int kb1, const int kb_end,
+    const SyTiles& T, const SyLane& L) {
+  for (int kb = kb0; kb < kb1; ++kb) {
+    syrk_stage_write<HILO>(sv, T, L.tid);   // LDS free: readers passed barrier
+    __syncthreads();
+    if (kb + 1 < kb_end) syrk_stage_load<HILO>(sv, P, i0, j0, kb + 1, L.tid);
+    syrk_products<HILO>(acc, T, L);
+    __syncthreads();
+  }
+}
+
+// ---------------------------------------------------------------------------
+// syrk_bf16: KK[m, m] += K^T K, split-K over the chunk rows for occupancy
+// ---------------------------------------------------------------------------
+// Grid: (ntile^2, split_k); lower-triangle tile indices exit at once.
+// Diagonal tiles (ti == tj) compute the full SY_CT x SY_CT tile and write it
+// (the a/b loops cover both halves), so no mirror is needed there; the
+// mirror fills the strict lower triangle from the strict upper tiles,
+// leaving KK fully populated.
+// Resources on gfx950 (hipcc -O3, -Rpass-analysis=kernel-resource-usage):
+// <false>: 198 VGPRs, 0 AGPRs, 0 B scratch, 40,960 B LDS; <true>: 256 VGPRs,
+// 0 AGPRs, 0 B scratch, 81,920 B LDS; both 2 waves/SIMD.
+
 template <bool HILO>
 __global__ void __launch_bounds__(SY_WG, 2)  // force 2 waves/SIMD occupancy
 syrk_bf16_kernel(const bf16* __restrict__ KcT,  // [m, cpitch] hi^T
@@ -351,160 +608,28 @@ syrk_bf16_kernel(const bf16* __restrict__ KcT,  // [m, cpitch] hi^T
                  const int c, const int m, const int cpitch, const int ntile,
                  const int split_k,
                  float* __restrict__ KK) {      // [m, m] accumulated
-  // with HILO: KK += hi^T hi + hi^T lo + lo^T hi  (lo^T lo ~ 2^-32, dropped)
-  // Operands arrive TRANSPOSED ([m, c], written for free by the cross
-  // kernel's register tile), so k runs along the contiguous axis: staging
-  // is one uint4 global load (8 lanes = one full 128-B line) + one
-  // conflict-free b128 LDS write per thread, and every MFMA fragment is
-  // one b128 LDS read.  The old [c, m]-operand versions were LDS- or
-  // VMEM-instruction bound (8 scalar ops per fragment either way).
   __shared__ __align__(16) bf16 lt[SY_CT * SY_STR];
   __shared__ __align__(16) bf16 rt[SY_CT * SY_STR];
   __shared__ __align__(16) bf16 ltl[HILO ? SY_CT * SY_STR : 1];
   __shared__ __align__(16) bf16 rtl[HILO ? SY_CT * SY_STR : 1];
+  const SyTiles T = {lt, rt, ltl, rtl};
 
   const int tile = blockIdx.x;
   const int ti = tile / ntile, tj = tile % ntile;
   if (tj < ti) return;                     // upper-triangle tiles only
   const int i0 = ti * SY_CT, j0 = tj * SY_CT;
-  const int slice = blockIdx.y;
-  const int kblocks = (c + SY_BK - 1) / SY_BK;
-  const int per = (kblocks + split_k - 1) / split_k;
-  const int kb0 = slice * per;
-  const int kb1 = min(kblocks, kb0 + per);
-  if (kb0 >= kb1) return;
+  int kb0, kb1;
+  if (!syrk_kslice(c, split_k, blockIdx.y, kb0, kb1)) return;
 
-  const int tid = threadIdx.x;
-  const int wave = tid >> 6;              // 0..7
-  const int lane = tid & 63;
-  const int wr = (wave >> 1) * 64;        // wave row offset in tile
-  const int wc = (wave & 1) * 128;        // wave col offset in tile
-
-  f32x4 acc[4][8];
-#pragma unroll
-  for (int a = 0; a < 4; ++a)
-#pragma unroll
-    for (int b = 0; b < 8; ++b) acc[a][b] = {0.f, 0.f, 0.f, 0.f};
-
-  const int l16 = lane & 15;              // fragment row/col
-  const int kgrp = lane >> 4;             // 0..3 -> k-subblock of 8
-  const bool vec_ok = (cpitch % 8 == 0);  // 16-B aligned row starts
-
-  // staging: thread -> (column, 8-deep k segment); 256 cols x 4 segs =
-  // 1024 slots per operand = 2 iterations of 512 threads.  Adjacent 4
-  // lanes take the 4 k-segments of one column (64-B half-lines; the other
-  // half of each 128-B line is the next k-block's data and hits L2).
-  //
-  // Single-buffer T14 register pipeline: the loads for block kb+1 are
-  // issued before the MFMA phase of block kb, which covers their latency;
-  // the per-CU VMEM return rate (~10 B/cyc HBM-bound) is the wall, which
-  // is why the tile is as large as LDS allows (bytes/flop ~ (M+N)/(M*N)).
-  auto load4 = [&](const bf16* mat, int c0, int col, int gk0) -> uint4 {
-    uint4 v;
-    bf16* vals = (bf16*)&v;
-    const int gc = c0 + col;
-    if (gc < m && vec_ok && gk0 + 8 <= c) {
-      v = *(const uint4*)(mat + (size_t)gc * cpitch + gk0);
-    } else if (gc < m) {
-#pragma unroll
-      for (int u = 0; u < 8; ++u)
-        vals[u] = (gk0 + u < c) ? mat[(size_t)gc * cpitch + gk0 + u]
-                                : (bf16)0.f;
-    } else {
-#pragma unroll
-      for (int u = 0; u < 8; ++u) vals[u] = (bf16)0.f;
-    }
-    return v;
-  };
-
-  uint4 sv[2][4];                         // [iteration][operand] prefetch
-  auto load_all = [&](int kb) {
-#pragma unroll
-    for (int it = 0; it < 2; ++it) {
-      const int f = tid + it * SY_WG;     // 0..1023
-      const int col = f >> 2;
-      const int gk0 = kb * SY_BK + (f & 3) * 8;
-      sv[it][0] = load4(KcT, i0, col, gk0);
-      sv[it][1] = load4(KcT, j0, col, gk0);
-      if (HILO) {
-        sv[it][2] = load4(KlT, i0, col, gk0);
-        sv[it][3] = load4(KlT, j0, col, gk0);
-      }
-    }
-  };
-  auto write_all = [&]() {
-#pragma unroll
-    for (int it = 0; it < 2; ++it) {
-      const int f = tid + it * SY_WG;
-      const int o = (f >> 2) * SY_STR + (f & 3) * 8;
-      *(uint4*)&lt[o] = sv[it][0];
-      *(uint4*)&rt[o] = sv[it][1];
-      if (HILO) {
-        *(uint4*)&ltl[o] = sv[it][2];
-        *(uint4*)&rtl[o] = sv[it][3];
-      }
-    }
-  };
-  auto mfma_pass = [&](const bf16* at, const bf16* bt) {
-    // one product pass in two b-halves of 16 INDEPENDENT MFMAs (no
-    // accumulator chaining between consecutive issues); fb covers 4 of
-    // the 8 column tiles at a time to stay inside the register budget
-    bf16x8 fa[4], fb[4];
-    const int ko = kgrp * 8;
-#pragma unroll
-    for (int a = 0; a < 4; ++a)
-      fa[a] = *(const bf16x8*)&at[(wr + a * 16 + l16) * SY_STR + ko];
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-#pragma unroll
-      for (int b = 0; b < 4; ++b)
-        fb[b] = *(const bf16x8*)&bt[(wc + (h * 4 + b) * 16 + l16) * SY_STR
-                                    + ko];
-#pragma unroll
-      for (int a = 0; a < 4; ++a)
-#pragma unroll
-        for (int b = 0; b < 4; ++b)
-          acc[a][h * 4 + b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-              fa[a], fb[b], acc[a][h * 4 + b], 0, 0, 0);
-    }
-  };
-
-  load_all(kb0);
-  for (int kb = kb0; kb < kb1; ++kb) {
-    write_all();                          // LDS free: readers passed barrier
-    __syncthreads();
-    if (kb + 1 < kb1) load_all(kb + 1);   // covered by the MFMA phase
-    mfma_pass(lt, rt);                    // hi * hi
-    if (HILO) {
-      mfma_pass(lt, rtl);                 // hi * lo
-      mfma_pass(ltl, rt);                 // lo * hi
-    }
-    __syncthreads();
-  }
-
-  // epilogue: C/D layout for 16x16x32: col = lane&15, row = (lane>>4)*4 + r
-  const int crow_base = (lane >> 4) * 4;
-  const int ccol = lane & 15;
-#pragma unroll
-  for (int a = 0; a < 4; ++a)
-#pragma unroll
-    for (int b = 0; b < 8; ++b)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int gi = i0 + wr + a * 16 + crow_base + r;
-        const int gj = j0 + wc + b * 16 + ccol;
-        if (gi < m && gj < m) {
-          atomicAdd(&KK[(size_t)gi * m + gj], acc[a][b][r]);
-          if (ti != tj)          // mirror off-diagonal tiles
-            atomicAdd(&KK[(size_t)gj * m + gi], acc[a][b][r]);
-        }
-      }
+  const SyLane L = sy_lane();
+  const SyOperands P = {KcT, KlT, c, m, cpitch};
+  SyAcc acc;
+  sy_zero(acc);
+  SyPrefetch sv;
+  syrk_stage_load<HILO>(sv, P, i0, j0, kb0, L.tid);
+  syrk_staged_steps<HILO>(acc, sv, P, i0, j0, kb0, kb1, kb1, T, L);
+  syrk_epilogue<true>(acc, KK, m, i0, j0, ti != tj, L.wr, L.wc, L.l16, L.kgrp);
 }
-
-// Diagonal tiles (ti == tj) compute the full SY_CT x SY_CT tile and write it
-// (the a/b loops cover both halves), so no mirror is needed there; the
-// mirror above fills the strict lower triangle from the strict upper tiles,
-// leaving KK fully populated.
 
 // ---------------------------------------------------------------------------
 // syrk_fused_gen: the SYRK above with its operands GENERATED in the block
@@ -515,14 +640,15 @@ syrk_bf16_kernel(const bf16* __restrict__ KcT,  // [m, cpitch] hi^T
 // every block recomputes the two 32 x 256 operand windows of its k-step:
 //
 //  * tile geometry, wave layout, accumulators, the three bf16 MFMA passes
-//    and the atomic epilogue are syrk_bf16_kernel<true>'s;
+//    and the atomic epilogue are the shared tile body above, as in
+//    syrk_bf16_kernel<true>;
 //  * where that kernel prefetches k-block kb+1 into registers around the
 //    MFMA phase of kb, this one generates it: wave w owns the 16-column
 //    groups 2w and 2w+1 of each window and both 16-row halves of the
 //    k-block, i.e. 8 fragments (4 on a diagonal tile) of
-//    mfma_f32_16x16x4_f32 over d, then cross_mfma_kernel's epilogue
-//    (q = nx + na - 2 dot clamped at 0, v = amp exp(-q), hi/lo split) in the
-//    same d order, so the values are the numbers that kernel would store;
+//    mfma_f32_16x16x4_f32 over d in cross_mfma_kernel's d order, then that
+//    kernel's knm_value() and split_hilo(), so the values are the numbers
+//    it would store;
 //  * the f32 D layout (col = lane&15, row = (lane>>4)*4 + r) hands each
 //    lane 4 consecutive k of one column: one 8-B store per operand into the
 //    k-major LDS tiles (80-B column pitch: conflict-free per half-wave),
@@ -549,9 +675,18 @@ syrk_bf16_kernel(const bf16* __restrict__ KcT,  // [m, cpitch] hi^T
 // Resources on gfx950 (hipcc -O3, -Rpass-analysis=kernel-resource-usage):
 // 234 VGPRs, 0 AGPRs, 0 B scratch, no spills, 160,256 B LDS,
 // 2 waves/SIMD (one 8-wave block per CU).
+//
+// This kernel sits 22 VGPRs under the limit and its register allocation
+// follows small changes of form.  It shares syrk_mfma_pass, syrk_epilogue,
+// syrk_kslice, knm_value and split_hilo with the other kernels; the
+// compiler emits the same instructions for it with or without that sharing.
+// Three small pieces stay written out in sf_tile because every shared form
+// tried moved the allocation (up to 242 VGPRs, or 36 B of scratch): the
+// lane decomposition and accumulator zeroing (sy_lane / sy_zero), the
+// fenced three-pass product sequence (syrk_products has no barriers and no
+// diagonal aliasing), and the mfma_pass lambda around syrk_mfma_pass.
 
-#define SF_DMAX 32
-#define SF_XSTR 36    // X' staging pitch in floats: 32 d-slots, nx, y, pad;
+#define SF_XSTR 36   // X' staging pitch in floats: 32 d-slots, nx, y, pad;
                       // 36*l16 mod 64 is a permutation of 4-bank blocks, so
                       // the A-fragment reads (l16 rows x 4 k) are conflict-free
 
@@ -567,6 +702,7 @@ sf_tile(const float* __restrict__ Xs, const float* __restrict__ As,
         float* __restrict__ xs, float* __restrict__ aw,
         double* __restrict__ Ky, float* __restrict__ KK) {
   constexpr int NG = DIAG ? 2 : 4;        // generated column groups per wave
+  // sy_lane() and sy_zero(), written out (see the note above)
   const int tid = threadIdx.x;
   const int wave = tid >> 6;              // 0..7
   const int lane = tid & 63;
@@ -576,7 +712,7 @@ sf_tile(const float* __restrict__ Xs, const float* __restrict__ As,
   const int kgrp = lane >> 4;
   const int crow = kgrp * 4;              // f32 D fragment: first row of 4
 
-  f32x4 acc[4][8];
+  SyAcc acc;
 #pragma unroll
   for (int a = 0; a < 4; ++a)
 #pragma unroll
@@ -675,13 +811,10 @@ sf_tile(const float* __restrict__ Xs, const float* __restrict__ As,
         float kysum = 0.f;
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          const float q = nxr[r] + nav[g] - 2.0f * dacc[rg][g][r];
-          float v = amp * __expf(-(q > 0.f ? q : 0.f));
+          float v = knm_value(nxr[r], nav[g], dacc[rg][g][r], amp);
           v = (cok[g] && gr0 + r < c) ? v : 0.f;   // exact zeros outside
           if (DIAG) kysum += v * yr[r];            // y stages 0 for rows >= c
-          const bf16 h = (bf16)v;
-          th[r] = h;
-          tl[r] = (bf16)(v - (float)h);
+          split_hilo(v, th[r], tl[r]);
         }
         gh[rg][g] = *(uint2*)th;
         gl[rg][g] = *(uint2*)tl;
@@ -701,24 +834,7 @@ sf_tile(const float* __restrict__ Xs, const float* __restrict__ As,
       }
   };
   auto mfma_pass = [&](const bf16* at, const bf16* bt) {
-    bf16x8 fa[4], fb[4];
-    const int ko = kgrp * 8;
-#pragma unroll
-    for (int a = 0; a < 4; ++a)
-      fa[a] = *(const bf16x8*)&at[(wr + a * 16 + l16) * SY_STR + ko];
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-#pragma unroll
-      for (int b = 0; b < 4; ++b)
-        fb[b] = *(const bf16x8*)&bt[(wc + (h * 4 + b) * 16 + l16) * SY_STR
-                                    + ko];
-#pragma unroll
-      for (int a = 0; a < 4; ++a)
-#pragma unroll
-        for (int b = 0; b < 4; ++b)
-          acc[a][h * 4 + b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-              fa[a], fb[b], acc[a][h * 4 + b], 0, 0, 0);
-    }
+    syrk_mfma_pass(acc, at, bt, wr, wc, l16, kgrp);
   };
 
   gload(kb0);
@@ -748,21 +864,7 @@ sf_tile(const float* __restrict__ Xs, const float* __restrict__ As,
     mfma_pass(ltl, DIAG ? lt : rt);       // lo * hi
   }
 
-  // epilogue: C/D layout for 16x16x32: col = lane&15, row = (lane>>4)*4 + r
-#pragma unroll
-  for (int a = 0; a < 4; ++a)
-#pragma unroll
-    for (int b = 0; b < 8; ++b)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int gi = i0 + wr + a * 16 + crow + r;
-        const int gj = j0 + wc + b * 16 + l16;
-        if (gi < m && gj < m) {
-          atomicAdd(&KK[(size_t)gi * m + gj], acc[a][b][r]);
-          if (!DIAG)             // mirror off-diagonal tiles
-            atomicAdd(&KK[(size_t)gj * m + gi], acc[a][b][r]);
-        }
-      }
+  syrk_epilogue<true>(acc, KK, m, i0, j0, !DIAG, wr, wc, l16, kgrp);
 
   if (DIAG) {
     // the 4 k-groups of a wave hold partials of the same 16 columns
@@ -799,11 +901,8 @@ syrk_fused_gen_kernel(const float* __restrict__ Xs,   // [c, d] pre-scaled
   int ti = 0, rem = blockIdx.x;
   while (rem >= ntile - ti) { rem -= ntile - ti; ++ti; }
   const int tj = ti + rem;
-  const int kblocks = (c + SY_BK - 1) / SY_BK;
-  const int per = (kblocks + split_k - 1) / split_k;
-  const int kb0 = blockIdx.y * per;
-  const int kb1 = min(kblocks, kb0 + per);
-  if (kb0 >= kb1) return;                 // empty slice (block-uniform)
+  int kb0, kb1;                           // empty slice: block-uniform exit
+  if (!syrk_kslice(c, split_k, blockIdx.y, kb0, kb1)) return;
 
   if (ti == tj)
     sf_tile<true>(Xs, As, nx, na, amp, yv, c, m, d, ti * SY_CT, tj * SY_CT,
@@ -827,6 +926,10 @@ syrk_fused_gen_kernel(const float* __restrict__ Xs,   // [c, d] pre-scaled
 // dependency between blocks, so a timeout only loses locality, never
 // correctness — no grid-residency assumption, no deadlock risk.
 
+// Resources on gfx950 (same flags as above):
+// <false>: 198 VGPRs, 0 AGPRs, 0 B scratch, 40,960 B LDS; <true>: 254 VGPRs,
+// 0 AGPRs, 0 B scratch, 81,920 B LDS; both 2 waves/SIMD.
+
 template <bool HILO>
 __global__ void __launch_bounds__(SY_WG, 2)
 syrk_bf16_sync_kernel(const bf16* __restrict__ KcT,   // [m, cpitch] hi^T
@@ -841,115 +944,28 @@ syrk_bf16_sync_kernel(const bf16* __restrict__ KcT,   // [m, cpitch] hi^T
   const int tj = tiles[2 * blockIdx.x + 1];
   if (ti < 0) return;
   const int i0 = ti * SY_CT, j0 = tj * SY_CT;
-  const int kblocks = (c + SY_BK - 1) / SY_BK;
+  const int kblocks = syrk_kblocks(c);
 
   __shared__ __align__(16) bf16 lt[SY_CT * SY_STR];
   __shared__ __align__(16) bf16 rt[SY_CT * SY_STR];
   __shared__ __align__(16) bf16 ltl[HILO ? SY_CT * SY_STR : 1];
   __shared__ __align__(16) bf16 rtl[HILO ? SY_CT * SY_STR : 1];
+  const SyTiles T = {lt, rt, ltl, rtl};
 
-  const int tid = threadIdx.x;
-  const int wave = tid >> 6;
-  const int lane = tid & 63;
-  const int wr = (wave >> 1) * 64;
-  const int wc = (wave & 1) * 128;
-
-  f32x4 acc[4][8];
-#pragma unroll
-  for (int a = 0; a < 4; ++a)
-#pragma unroll
-    for (int b = 0; b < 8; ++b) acc[a][b] = {0.f, 0.f, 0.f, 0.f};
-
-  const int l16 = lane & 15;
-  const int kgrp = lane >> 4;
-  const bool vec_ok = (cpitch % 8 == 0);
-
-  auto load4 = [&](const bf16* mat, int c0, int col, int gk0) -> uint4 {
-    uint4 v;
-    bf16* vals = (bf16*)&v;
-    const int gc = c0 + col;
-    if (gc < m && vec_ok && gk0 + 8 <= c) {
-      v = *(const uint4*)(mat + (size_t)gc * cpitch + gk0);
-    } else if (gc < m) {
-#pragma unroll
-      for (int u = 0; u < 8; ++u)
-        vals[u] = (gk0 + u < c) ? mat[(size_t)gc * cpitch + gk0 + u]
-                                : (bf16)0.f;
-    } else {
-#pragma unroll
-      for (int u = 0; u < 8; ++u) vals[u] = (bf16)0.f;
-    }
-    return v;
-  };
-
-  uint4 sv[2][4];
-  auto load_all = [&](int kb) {
-#pragma unroll
-    for (int it = 0; it < 2; ++it) {
-      const int f = tid + it * SY_WG;
-      const int col = f >> 2;
-      const int gk0 = kb * SY_BK + (f & 3) * 8;
-      sv[it][0] = load4(KcT, i0, col, gk0);
-      sv[it][1] = load4(KcT, j0, col, gk0);
-      if (HILO) {
-        sv[it][2] = load4(KlT, i0, col, gk0);
-        sv[it][3] = load4(KlT, j0, col, gk0);
-      }
-    }
-  };
-  auto write_all = [&]() {
-#pragma unroll
-    for (int it = 0; it < 2; ++it) {
-      const int f = tid + it * SY_WG;
-      const int o = (f >> 2) * SY_STR + (f & 3) * 8;
-      *(uint4*)&lt[o] = sv[it][0];
-      *(uint4*)&rt[o] = sv[it][1];
-      if (HILO) {
-        *(uint4*)&ltl[o] = sv[it][2];
-        *(uint4*)&rtl[o] = sv[it][3];
-      }
-    }
-  };
-  auto mfma_pass = [&](const bf16* at, const bf16* bt) {
-    bf16x8 fa[4], fb[4];
-    const int ko = kgrp * 8;
-#pragma unroll
-    for (int a = 0; a < 4; ++a)
-      fa[a] = *(const bf16x8*)&at[(wr + a * 16 + l16) * SY_STR + ko];
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-#pragma unroll
-      for (int b = 0; b < 4; ++b)
-        fb[b] = *(const bf16x8*)&bt[(wc + (h * 4 + b) * 16 + l16) * SY_STR
-                                    + ko];
-#pragma unroll
-      for (int a = 0; a < 4; ++a)
-#pragma unroll
-        for (int b = 0; b < 4; ++b)
-          acc[a][h * 4 + b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-              fa[a], fb[b], acc[a][h * 4 + b], 0, 0, 0);
-    }
-  };
-
-  load_all(0);
+  const SyLane L = sy_lane();
+  const SyOperands P = {KcT, KlT, c, m, cpitch};
+  SyAcc acc;
+  sy_zero(acc);
+  SyPrefetch sv;
+  syrk_stage_load<HILO>(sv, P, i0, j0, 0, L.tid);
   const int nphases = (kblocks + kpb - 1) / kpb;
   for (int p = 0; p < nphases; ++p) {
-    const int kb1 = min(kblocks, (p + 1) * kpb);
-    for (int kb = p * kpb; kb < kb1; ++kb) {
-      write_all();
-      __syncthreads();
-      if (kb + 1 < kblocks) load_all(kb + 1);
-      mfma_pass(lt, rt);
-      if (HILO) {
-        mfma_pass(lt, rtl);
-        mfma_pass(ltl, rt);
-      }
-      __syncthreads();
-    }
+    syrk_staged_steps<HILO>(acc, sv, P, i0, j0, p * kpb,
+                            min(kblocks, (p + 1) * kpb), kblocks, T, L);
     // best-effort pacing: arrive, then wait (bounded) for the cohort.
     // Relaxed atomics only — nothing is communicated, so no fences.
     if (p + 1 < nphases) {
-      if (tid == 0) {
+      if (L.tid == 0) {
         __hip_atomic_fetch_add(&phase_ctr[p], 1, __ATOMIC_RELAXED,
                                __HIP_MEMORY_SCOPE_AGENT);
         int spins = 0;
@@ -962,22 +978,8 @@ syrk_bf16_sync_kernel(const bf16* __restrict__ KcT,   // [m, cpitch] hi^T
     }
   }
 
-  // epilogue: single owner per element per launch -> plain accumulate
-  const int crow_base = (lane >> 4) * 4;
-  const int ccol = lane & 15;
-#pragma unroll
-  for (int a = 0; a < 4; ++a)
-#pragma unroll
-    for (int b = 0; b < 8; ++b)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int gi = i0 + wr + a * 16 + crow_base + r;
-        const int gj = j0 + wc + b * 16 + ccol;
-        if (gi < m && gj < m) {
-          KK[(size_t)gi * m + gj] += acc[a][b][r];
-          if (ti != tj) KK[(size_t)gj * m + gi] += acc[a][b][r];
-        }
-      }
+  // single owner per element per launch -> plain accumulate
+  syrk_epilogue<false>(acc, KK, m, i0, j0, ti != tj, L.wr, L.wc, L.l16, L.kgrp);
 }
 
 // ---------------------------------------------------------------------------
@@ -1069,8 +1071,6 @@ extern "C" hipError_t launch_syrk_bf16(const void* KcT, const void* KlT,
   }
   return hipGetLastError();
 }
-
-extern "C" int syrk_fused_gen_dmax() { return SF_DMAX; }
 
 extern "C" hipError_t launch_syrk_fused_gen(
     const float* Xs, const float* As, const float* nx, const float* na,

@@ -54,6 +54,7 @@
 
 #define WG 512
 #include "linalg_lds.h"
+#include "kernel_geom.h"
 
 typedef __attribute__((ext_vector_type(4))) float mfma_f32x4;
 
@@ -72,47 +73,15 @@ struct NllLds {
   int* bad;     // 1
 };
 
-// Every region is padded to 16 B so the vectorized dots can assume
-// aligned bases.  Keep in EXACT sync with the mirror in bindings.cpp.
-static __host__ __device__ inline size_t nll_sa(int k) {
-  return (size_t)((k + 4) & ~3);                       // k+1 up to mult 4
-}
-
-static __host__ __device__ inline size_t nll_tsz(int k) {
-  size_t t = (size_t)k * 36;
-  if (t < 32 * nll_sa(k)) t = 32 * nll_sa(k);
-  if (t < 448) t = 448;
-  return t;
-}
-
-static __host__ __device__ inline size_t a16(size_t n) {
-  return (n + 15) & ~(size_t)15;
-}
-
-static __host__ __device__ inline size_t nll_dp4(int d) {
-  return (size_t)((d + 4) & ~3);     // X row stride: 16-B aligned rows
-}
-
-static __host__ __device__ inline size_t nll_lds_bytes2(int k, int d) {
-  size_t off = 0;
-  off += a16(sizeof(double) * 10);                     // red + misc
-  off += a16(sizeof(float) * (size_t)k * nll_sa(k));   // A
-  off += a16(sizeof(float) * nll_tsz(k));              // T
-  off += a16(sizeof(float) * (size_t)k * nll_dp4(d));  // X
-  off += 4 * a16(sizeof(float) * k);                   // yb alpha tvec rrow
-  off += a16(sizeof(float) * d);                       // s2
-  off += 16;                                           // bad (+pad)
-  return off;
-}
-
+// Region sizes: kernel_geom.h (nll_lds_bytes lists them in this order).
 __device__ inline NllLds carve(char* base, int k, int d) {
   NllLds L;
   char* p = base;
   L.red = (double*)p;   L.misc = L.red + 8;
   p += a16(sizeof(double) * 10);
-  L.A = (float*)p;      p += a16(sizeof(float) * (size_t)k * nll_sa(k));
-  L.T = (float*)p;      p += a16(sizeof(float) * nll_tsz(k));
-  L.X = (float*)p;      p += a16(sizeof(float) * (size_t)k * nll_dp4(d));
+  L.A = (float*)p;      p += a16(sizeof(float) * (size_t)k * geom_sa(k));
+  L.T = (float*)p;      p += a16(sizeof(float) * geom_tsz(k));
+  L.X = (float*)p;      p += a16(sizeof(float) * (size_t)k * geom_dp4(d));
   L.yb = (float*)p;     p += a16(sizeof(float) * k);
   L.alpha = (float*)p;  p += a16(sizeof(float) * k);
   L.tvec = (float*)p;   p += a16(sizeof(float) * k);
@@ -140,8 +109,8 @@ fused_expert_nll_kernel(const float* __restrict__ Xg,
     out_clk[(size_t)blockIdx.x * 20 + (n)] = wall_clock64(); } while (0)
   PH(0);
   NllLds S = carve(lds_raw, k, d);
-  const int SA = (int)nll_sa(k);
-  const int dp = (int)nll_dp4(d);
+  const int SA = (int)geom_sa(k);
+  const int dp = (int)geom_dp4(d);
   const int e = blockIdx.x;
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -406,13 +375,13 @@ extern "C" hipError_t launch_fused_expert_nll(
     double* out_nll, double* out_sumW0, double* out_trG, double* out_contr,
     int* out_bad, unsigned long long* out_clk, hipStream_t stream,
     size_t* lds_used) {
-  size_t lds = nll_lds_bytes2(k, d);
+  size_t lds = nll_lds_bytes(k, d);
   // occupancy experiment knob: force 1 WG/CU by padding the LDS ask
   // (measures how much the usual 2 co-resident expert WGs overlap)
   if (const char* pad = getenv("SPARK_GP_AMD_NLL_LDS_PAD"))
     lds += (size_t)atol(pad);
   if (lds_used) *lds_used = lds;
-  if (lds > 160 * 1024 || k > 128 || d > 128)
+  if (lds > GEOM_LDS_MAX || k > 128 || d > 128)
     return hipErrorInvalidConfiguration;
   hipLaunchKernelGGL(fused_expert_nll_kernel, dim3(E), dim3(WG), lds, stream,
                      X, y, scale, amp, noise, k, d,

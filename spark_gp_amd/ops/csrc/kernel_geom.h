@@ -1,0 +1,76 @@
+// Kernel geometry shared by the device code and the host-side gates: the
+// LDS budgets of the fused expert kernels and the SYRK tile constants.
+// Included by expert_nll.hip, laplace.hip, cross_syrk.hip (hipcc) and by
+// bindings.cpp (host compiler), so a *_supported() answer and the launch it
+// guards are computed by the same function.
+#pragma once
+#include <stddef.h>
+
+#ifdef __HIPCC__
+#define GEOM_HD __host__ __device__
+#else
+#define GEOM_HD
+#endif
+
+// ---- fused expert kernels (expert_nll.hip, laplace.hip) -------------------
+// Every LDS region is padded to 16 B so the vectorized dots can assume
+// aligned bases.
+
+// row stride of the k x k working buffer: k+1 up to a multiple of 4
+static GEOM_HD inline size_t geom_sa(int k) {
+  return (size_t)((k + 4) & ~3);
+}
+
+// temp buffer: max(k*36, 32*SA, 448) floats
+static GEOM_HD inline size_t geom_tsz(int k) {
+  size_t t = (size_t)k * 36;
+  if (t < 32 * geom_sa(k)) t = 32 * geom_sa(k);
+  if (t < 448) t = 448;
+  return t;
+}
+
+static GEOM_HD inline size_t a16(size_t n) {
+  return (n + 15) & ~(size_t)15;
+}
+
+// X row stride: 16-B aligned rows
+static GEOM_HD inline size_t geom_dp4(int d) {
+  return (size_t)((d + 4) & ~3);
+}
+
+// LDS bytes of fused_expert_nll_kernel; region order is NllLds's carve
+static GEOM_HD inline size_t nll_lds_bytes(int k, int d) {
+  size_t off = 0;
+  off += a16(sizeof(double) * 10);                      // red + misc
+  off += a16(sizeof(float) * (size_t)k * geom_sa(k));   // A
+  off += a16(sizeof(float) * geom_tsz(k));              // T
+  off += a16(sizeof(float) * (size_t)k * geom_dp4(d));  // X
+  off += 4 * a16(sizeof(float) * k);                    // yb alpha tvec rrow
+  off += a16(sizeof(float) * d);                        // s2
+  off += 16;                                            // bad (+pad)
+  return off;
+}
+
+// LDS bytes of fused_laplace_kernel<ev>; region order is lap_carve's
+static GEOM_HD inline size_t lap_lds_bytes(int k, int d, int ev = 0) {
+  size_t off = a16(sizeof(double) * 10);
+  off += a16(sizeof(float) * (size_t)k * geom_sa(k));   // A
+  off += a16(sizeof(float) * (size_t)k * geom_dp4(d));  // X
+  off += a16(sizeof(float) * geom_tsz(k));
+  off += 8 * a16(sizeof(float) * k);
+  off += a16(sizeof(float) * d);
+  if (ev) {
+    off += 2 * a16(sizeof(float) * k);        // vv + s2v
+    off += a16(sizeof(float) * d);            // betav
+    off += a16(sizeof(double) * (d + 2));     // gout
+  }
+  off += 16;
+  return off;
+}
+
+#define GEOM_LDS_MAX (160 * 1024)   // LDS per workgroup on gfx950
+
+// ---- SYRK kernels (cross_syrk.hip) ----------------------------------------
+#define SY_CT 256     // output tile edge (per block)
+#define SY_BK 32      // k rows per staged block
+#define SF_DMAX 32    // syrk_fused_gen: d-slots per row that fit its LDS

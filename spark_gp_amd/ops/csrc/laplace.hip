@@ -39,6 +39,7 @@
 
 #define WG 512
 #include "linalg_lds.h"
+#include "kernel_geom.h"
 
 struct LapLds {
   float* X;     // k * dp4: raw features (16-B-aligned rows)
@@ -65,67 +66,30 @@ struct LapLds {
   int* bad;     // 1
 };
 
-// Regions padded to 16 B (vectorized dots assume aligned bases); keep in
-// EXACT sync with the mirror in bindings.cpp.
-static __host__ __device__ inline size_t lap_sa(int k) {
-  return (size_t)((k + 4) & ~3);                       // k+1 up to mult 4
-}
-
-static __host__ __device__ inline size_t lap_tsz(int k) {
-  size_t t = (size_t)k * 36;
-  if (t < 32 * lap_sa(k)) t = 32 * lap_sa(k);
-  if (t < 448) t = 448;
-  return t;
-}
-
-static __host__ __device__ inline size_t lap_a16(size_t n) {
-  return (n + 15) & ~(size_t)15;
-}
-
-static __host__ __device__ inline size_t lap_dp4(int d) {
-  return (size_t)((d + 4) & ~3);
-}
-
-static __host__ __device__ inline size_t lap_lds_bytes(int k, int d,
-                                                       int ev = 0) {
-  size_t off = lap_a16(sizeof(double) * 10);
-  off += lap_a16(sizeof(float) * (size_t)k * lap_sa(k));      // A
-  off += lap_a16(sizeof(float) * (size_t)k * lap_dp4(d));     // X
-  off += lap_a16(sizeof(float) * lap_tsz(k));
-  off += 8 * lap_a16(sizeof(float) * k);
-  off += lap_a16(sizeof(float) * d);
-  if (ev) {
-    off += 2 * lap_a16(sizeof(float) * k);       // vv + s2v
-    off += lap_a16(sizeof(float) * d);           // betav
-    off += lap_a16(sizeof(double) * (d + 2));    // gout
-  }
-  off += 16;
-  return off;
-}
-
+// Region sizes: kernel_geom.h (lap_lds_bytes lists them in this order).
 template <bool EV>
 __device__ inline LapLds lap_carve(char* base, int k, int d) {
   LapLds L;
   char* p = base;
   L.red = (double*)p;  L.misc = L.red + 8;
-  p += lap_a16(sizeof(double) * 10);
-  L.A = (float*)p;     p += lap_a16(sizeof(float) * (size_t)k * lap_sa(k));
-  L.X = (float*)p;     p += lap_a16(sizeof(float) * (size_t)k * lap_dp4(d));
-  L.T = (float*)p;     p += lap_a16(sizeof(float) * lap_tsz(k));
-  L.yb = (float*)p;    p += lap_a16(sizeof(float) * k);
-  L.fb = (float*)p;    p += lap_a16(sizeof(float) * k);
-  L.pi = (float*)p;    p += lap_a16(sizeof(float) * k);
-  L.sqw = (float*)p;   p += lap_a16(sizeof(float) * k);
-  L.bv = (float*)p;    p += lap_a16(sizeof(float) * k);
-  L.av = (float*)p;    p += lap_a16(sizeof(float) * k);
-  L.t1 = (float*)p;    p += lap_a16(sizeof(float) * k);
-  L.t2 = (float*)p;    p += lap_a16(sizeof(float) * k);
-  L.s2 = (float*)p;    p += lap_a16(sizeof(float) * d);
+  p += a16(sizeof(double) * 10);
+  L.A = (float*)p;     p += a16(sizeof(float) * (size_t)k * geom_sa(k));
+  L.X = (float*)p;     p += a16(sizeof(float) * (size_t)k * geom_dp4(d));
+  L.T = (float*)p;     p += a16(sizeof(float) * geom_tsz(k));
+  L.yb = (float*)p;    p += a16(sizeof(float) * k);
+  L.fb = (float*)p;    p += a16(sizeof(float) * k);
+  L.pi = (float*)p;    p += a16(sizeof(float) * k);
+  L.sqw = (float*)p;   p += a16(sizeof(float) * k);
+  L.bv = (float*)p;    p += a16(sizeof(float) * k);
+  L.av = (float*)p;    p += a16(sizeof(float) * k);
+  L.t1 = (float*)p;    p += a16(sizeof(float) * k);
+  L.t2 = (float*)p;    p += a16(sizeof(float) * k);
+  L.s2 = (float*)p;    p += a16(sizeof(float) * d);
   if (EV) {
-    L.vv = (float*)p;    p += lap_a16(sizeof(float) * k);
-    L.s2v = (float*)p;   p += lap_a16(sizeof(float) * k);
-    L.betav = (float*)p; p += lap_a16(sizeof(float) * d);
-    L.gout = (double*)p; p += lap_a16(sizeof(double) * (d + 2));
+    L.vv = (float*)p;    p += a16(sizeof(float) * k);
+    L.s2v = (float*)p;   p += a16(sizeof(float) * k);
+    L.betav = (float*)p; p += a16(sizeof(float) * d);
+    L.gout = (double*)p; p += a16(sizeof(double) * (d + 2));
   }
   L.bad = (int*)p;
   return L;
@@ -173,13 +137,13 @@ fused_laplace_kernel(const float* __restrict__ Xg,   // [E, k, d]
                      double* __restrict__ out_logz,     // [E]     (EV)
                      double* __restrict__ out_grad) {   // [E,d+2] (EV)
   extern __shared__ char lds_raw[];
-  const int SA = (int)lap_sa(k);
+  const int SA = (int)geom_sa(k);
   LapLds S = lap_carve<EV>(lds_raw, k, d);
   const int e = blockIdx.x;
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const float* Xe = Xg + (size_t)e * k * d;
-  const int dp = (int)lap_dp4(d);
+  const int dp = (int)geom_dp4(d);
 
   // ---- stage X, y, f, s2 -------------------------------------------
   for (int i = tid; i < k * d; i += WG) {
@@ -616,7 +580,7 @@ extern "C" hipError_t launch_fused_laplace_newton(
     hipStream_t stream, size_t* lds_used) {
   size_t lds = lap_lds_bytes(k, d);
   if (lds_used) *lds_used = lds;
-  if (lds > 160 * 1024 || k > 128 || d > k)
+  if (lds > GEOM_LDS_MAX || k > 128 || d > k)
     return hipErrorInvalidConfiguration;
   hipLaunchKernelGGL(fused_laplace_kernel<false>, dim3(E), dim3(WG), lds,
                      stream, X, y, f, scale, amp, noise, k, d, tol,
@@ -633,7 +597,7 @@ extern "C" hipError_t launch_fused_laplace_evidence(
     size_t* lds_used) {
   size_t lds = lap_lds_bytes(k, d, 1);
   if (lds_used) *lds_used = lds;
-  if (lds > 160 * 1024 || k > 128 || d > k)
+  if (lds > GEOM_LDS_MAX || k > 128 || d > k)
     return hipErrorInvalidConfiguration;
   hipLaunchKernelGGL(fused_laplace_kernel<true>, dim3(E), dim3(WG), lds,
                      stream, X, y, f, scale, amp, noise, k, d, tol,

@@ -479,6 +479,75 @@ def test_syrk_sync_matches_plain(dev, ext):
     assert err_sync < 4.0 * max(err_plain, 1e-30)
 
 
+_SMALL_M = 300      # two column windows (the second holds 44 real columns)
+                    # -> three tiles, one of them off-diagonal
+
+
+@pytest.fixture(scope="module")
+def syrk_small(dev):
+    """Operands and fp64 references of the small-shape SYRK tests, per c:
+    104 takes the 16-B vector loads with a partial last k-block, 100 is no
+    multiple of 8 so every operand load takes the scalar path."""
+    g = torch.Generator().manual_seed(21)
+    out = {}
+    for c in (104, 100):
+        V = torch.rand(c, _SMALL_M, generator=g).to(dev)
+        Kc = V.bfloat16()
+        Kl = (V - Kc.float()).bfloat16()
+        full = Kc.double() + Kl.double()
+        out[c] = {"KcT": Kc.T.contiguous(), "KlT": Kl.T.contiguous(),
+                  "ref_hilo": full.T @ full,
+                  "ref_hi": Kc.double().T @ Kc.double()}
+    return out
+
+
+def _syrk_small_run(ext, dev, KcT, KlT, sync, calls):
+    from spark_gp_amd.ops import hip_backend as hb
+    KK = torch.zeros(_SMALL_M, _SMALL_M, device=dev, dtype=torch.float32)
+    for _ in range(calls):
+        if sync:
+            # kpb = 1: one k-block per phase, so the pacing code runs
+            for tt, nact in hb._syrk_sync_tiles(_SMALL_M, dev):
+                ext.syrk_bf16_sync_acc(KcT, KlT, KK, tt, 1, nact)
+        else:
+            ext.syrk_bf16_acc(KcT, KlT, KK, 1)
+    return KK
+
+
+@pytest.mark.parametrize("hilo", [True, False])
+@pytest.mark.parametrize("c", [104, 100])
+def test_syrk_small_shapes_plain_and_sync(dev, ext, syrk_small, c, hilo):
+    """split_k = 1 and the k-synchronized kernel at a shape with partial
+    tiles, a partial k-block and (c = 100) the scalar staging path, against
+    the fp64 product of the represented operand values."""
+    s = syrk_small[c]
+    KcT, KlT = s["KcT"], (s["KlT"] if hilo else None)
+    ref = s["ref_hilo"] if hilo else s["ref_hi"]
+    once = {}
+    for sync in (False, True):
+        KK = _syrk_small_run(ext, dev, KcT, KlT, sync, 1)
+        once[sync] = KK
+        diff = (KK.double() - ref).abs()
+        if hilo:
+            err, scale = diff.max().item(), ref.abs().max().item()
+            print(f"c={c} hilo sync={sync}: err {err:.3e} scale {scale:.3e}")
+            assert err < 3e-5 * scale, (sync, err, scale)
+        else:
+            rel = float((diff / ref.abs().clamp_min(1.0)).max())
+            print(f"c={c} single sync={sync}: rel {rel:.3e}")
+            assert rel < 2e-2, (sync, rel)
+        # accumulation semantics: each element receives one addend per call
+        # (one k-slice, one owner tile), and x + x is exact in fp32
+        KK2 = _syrk_small_run(ext, dev, KcT, KlT, sync, 2)
+        assert torch.equal(KK2, 2 * KK), sync
+    if not hilo:
+        # same k order, one addend onto zero per element; the sync kernel's
+        # lower-triangle tile orientation only swaps the factors of each
+        # bf16 product.  (With hi/lo the two orientations add the cross
+        # terms in opposite order, so bit equality is not expected there.)
+        assert torch.equal(once[True], once[False])
+
+
 def test_greedy_provider_gpu_path(dev, ext):
     """Greedy selection on GPU (HIP cross-kernel + fp32 scoring): selects a
     usable active set — a fit with it must beat the same-size random set's
