@@ -30,7 +30,9 @@ def _fused_ab(rows, m, d):
     """--fused [d]: the whole PPA chunk both ways on the same inputs,
     alternating — cross_mfma_ppa + syrk_bf16_acc (the dispatch's split_k)
     against ppa_fused_acc over a split_k sweep.  Times are per chunk."""
-    from spark_gp_amd.ops.ppa_gate import ppa_fused_split_k
+    from spark_gp_amd.ops.ppa_plan import (ppa_fused_split_k,
+                                           syrk_staged_split_k,
+                                           syrk_tile_count)
     X = torch.rand(rows, d, device=dev)
     A = torch.rand(m, d, device=dev)
     y = torch.rand(rows, device=dev)
@@ -39,9 +41,8 @@ def _fused_ab(rows, m, d):
     nx, na = (Xs * Xs).sum(-1).contiguous(), (As * As).sum(-1).contiguous()
     KK = torch.zeros(m, m, device=dev)
     Ky = torch.zeros(m, dtype=torch.float64, device=dev)
-    ntile = (m + 255) // 256
-    tiles = ntile * (ntile + 1) // 2
-    sk_pair = max(1, min(16, round(4096 / tiles)))
+    tiles = syrk_tile_count(m)
+    sk_pair = syrk_staged_split_k(m)
 
     def pair():
         KcT, KlT = ext.cross_mfma_ppa(Xs, As, nx, na, 1.3, y, Ky)
@@ -93,9 +94,9 @@ Kl = (V - Kc.float()).to(torch.bfloat16)
 KcT = Kc.T.contiguous()              # SYRK takes transposed operands [m, c]
 KlT = Kl.T.contiguous()
 
-ntile = (m + 255) // 256
-tiles = ntile * (ntile + 1) // 2
-split_k = max(1, min(64, 256 // tiles))
+from spark_gp_amd.ops.ppa_plan import ppa_fused_split_k  # noqa: E402
+
+split_k = ppa_fused_split_k(m)      # fills the 256 CUs once
 print(f"rows={rows} m={m} split_k={split_k}")
 
 # numerics: KK vs fp64 of the REPRESENTED value (hi+lo), which is what the
@@ -143,10 +144,10 @@ if "--sweep" in sys.argv:
 
 # A/B the k-synchronized persistent path (m >= 4096)
 if "--sync" in sys.argv and m >= 4096:
-    import os as _os
     from spark_gp_amd.ops import hip_backend as hb
+    from spark_gp_amd.ops.ppa_plan import syrk_sync_patch
     launches = hb._syrk_sync_tiles(m, "cuda")
-    print(f"sync patch={_os.environ.get('SPARK_GP_AMD_SYRK_PATCH','2x4')}: "
+    print(f"sync patch={'x'.join(map(str, syrk_sync_patch()))}: "
           f"{len(launches)} launches, tiles {[n for _, n in launches]}")
 
     for kpb in (128,):

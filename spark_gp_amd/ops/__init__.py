@@ -38,41 +38,40 @@ def _load_hip():
     return _hip
 
 
-def _allow_fallback() -> bool:
-    return os.environ.get("SPARK_GP_AMD_ALLOW_TORCH_FALLBACK", "0") == "1"
-
-
-def _force_torch() -> bool:
-    """Debug/A-B switch: run the eager torch path even when HIP is present."""
-    return os.environ.get("SPARK_GP_AMD_FORCE_TORCH", "0") == "1"
+def _env_set(name: str) -> bool:
+    return os.environ.get(name, "0") == "1"
 
 
 def hip_available() -> bool:
     return _load_hip() is not None
 
 
-def _require_hip_or_fallback(what: str) -> bool:
-    """True -> use HIP; False -> torch fallback allowed; raises otherwise."""
-    if _load_hip() is not None:
-        return True
-    if _allow_fallback():
-        return False
-    raise RuntimeError(
-        f"{what}: running on a GPU but the spark_gp_amd HIP extension is not "
-        f"loadable ({_hip_err}); build it with `python setup.py build_ext "
-        f"--inplace` (PYTORCH_ROCM_ARCH=gfx950) or set "
-        f"SPARK_GP_AMD_ALLOW_TORCH_FALLBACK=1 to explicitly allow the eager "
-        f"PyTorch path")
+def _backend_for(what: str, t: torch.Tensor, required: bool = True):
+    """Which backend runs op ``what`` on tensor ``t``: the HIP backend
+    module, or None for the torch path (CPU tensor, the debug/A-B switch
+    SPARK_GP_AMD_FORCE_TORCH, or a missing extension where ``required`` or
+    the fallback switch allow it; raises otherwise)."""
+    if not t.is_cuda or _env_set("SPARK_GP_AMD_FORCE_TORCH"):
+        return None
+    hip = _load_hip()
+    if hip is None and required and \
+            not _env_set("SPARK_GP_AMD_ALLOW_TORCH_FALLBACK"):
+        raise RuntimeError(
+            f"{what}: running on a GPU but the spark_gp_amd HIP extension is "
+            f"not loadable ({_hip_err}); build it with `python setup.py "
+            f"build_ext --inplace` (PYTORCH_ROCM_ARCH=gfx950) or set "
+            f"SPARK_GP_AMD_ALLOW_TORCH_FALLBACK=1 to explicitly allow the "
+            f"eager PyTorch path")
+    return hip
 
 
 def nll_grad_compiled(cs: CompiledKernel, theta: np.ndarray,
                       X: torch.Tensor, y: torch.Tensor
                       ) -> Tuple[float, np.ndarray]:
-    if X.is_cuda and cs.base in ("ard", "rbf") and not _force_torch():
-        hip = _load_hip()
-        if _require_hip_or_fallback("nll_grad_compiled") and \
-                hip.supports_nll(cs, X):
-            return hip.nll_grad_compiled(cs, theta, X, y)
+    hip = (_backend_for("nll_grad_compiled", X)
+           if cs.base in ("ard", "rbf") else None)
+    if hip is not None and hip.supports_nll(cs, X):
+        return hip.nll_grad_compiled(cs, theta, X, y)
     return torch_backend.nll_grad_compiled(cs, theta, X, y)
 
 
@@ -84,19 +83,17 @@ def nll_grad_generic(kernel: Kernel, theta: np.ndarray,
 def laplace_nll_grad(kernel: Kernel, theta: np.ndarray, X: torch.Tensor,
                      y: torch.Tensor, f: torch.Tensor, tol: float,
                      max_newton_iter: int = 200, likelihood=None):
+    from ..kernels.compiled import compile_kernel
     from ..likelihoods import LogisticLikelihood
     logistic = likelihood is None or isinstance(likelihood,
                                                 LogisticLikelihood)
-    # the fused HIP Newton kernel implements the logistic link; other
-    # likelihoods run on the batched torch path
-    if X.is_cuda and logistic and not _force_torch():
-        from ..kernels.compiled import compile_kernel
-        cs = compile_kernel(kernel)
-        hip = _load_hip()
-        if (cs is not None
-                and _require_hip_or_fallback("laplace_nll_grad")
-                and tol >= hip.LAPLACE_MIN_TOL
-                and hip.supports_laplace_evidence(cs, X)):
+    # the fused HIP Newton kernel implements the logistic link on compiled
+    # kernels; everything else runs on the batched torch path
+    cs = compile_kernel(kernel) if X.is_cuda and logistic else None
+    hip = _backend_for("laplace_nll_grad", X) if cs is not None else None
+    if hip is not None:
+        if tol >= hip.LAPLACE_MIN_TOL and \
+                hip.supports_laplace_evidence(cs, X):
             # fully fused K10+K11: Newton AND the Algorithm 5.1 evidence
             # in one launch; None -> fp32 breakdown, warm torch fallback
             res = hip.laplace_evidence(cs, theta, X, y, f, tol,
@@ -105,9 +102,7 @@ def laplace_nll_grad(kernel: Kernel, theta: np.ndarray, X: torch.Tensor,
                 return res
             return torch_backend.laplace_nll_grad(
                 kernel, theta, X, y, f, tol, max_newton_iter)
-        if (cs is not None
-                and _require_hip_or_fallback("laplace_nll_grad")
-                and hip.supports_laplace(cs, X)):
+        if hip.supports_laplace(cs, X):
             # fused Newton loop runs each expert to convergence on the GPU
             # (updates f in place); the torch pass below then converges in
             # 2-3 cheap iterations and computes the Algorithm 5.1 evidence
@@ -133,19 +128,24 @@ def laplace_nll_grad(kernel: Kernel, theta: np.ndarray, X: torch.Tensor,
 def kmn_knm_and_kmny(kernel: Kernel, active: torch.Tensor,
                      X: torch.Tensor, y: torch.Tensor,
                      chunk_rows: int = 262144, precision: str = "fp64"):
-    if X.is_cuda and not _force_torch():
-        hip = _load_hip()
-        if _require_hip_or_fallback("kmn_knm_and_kmny") and \
-                hip.supports_ppa(kernel, X):
-            return hip.kmn_knm_and_kmny(kernel, active, X, y, chunk_rows,
-                                        precision)
+    hip = _backend_for("kmn_knm_and_kmny", X)
+    if hip is not None and hip.supports_ppa(kernel, X):
+        return hip.kmn_knm_and_kmny(kernel, active, X, y, chunk_rows,
+                                    precision)
     return torch_backend.kmn_knm_and_kmny(kernel, active, X, y, chunk_rows)
 
 
+def magic_vector_matrix(kernel: Kernel, KK: torch.Tensor, Ky: torch.Tensor,
+                        active: torch.Tensor):
+    """On the K13 kernels; None where ppa's CPU oracle should run."""
+    hip = _backend_for("magic_vector_matrix", KK)
+    return hip and hip.magic_vector_matrix(kernel, KK, Ky, active)
+
+
 def cross_kernel(kernel: Kernel, Xtest: torch.Tensor, Xtrain: torch.Tensor):
-    """Cross-kernel dispatch for prediction paths."""
-    if Xtest.is_cuda:
-        hip = _load_hip()
-        if hip is not None and hip.supports_ppa(kernel, Xtest):
-            return hip.cross_kernel(kernel, Xtest, Xtrain)
+    """Cross-kernel dispatch for prediction paths (the torch kernel serves
+    where the extension is missing)."""
+    hip = _backend_for("cross_kernel", Xtest, required=False)
+    if hip is not None and hip.supports_ppa(kernel, Xtest):
+        return hip.cross_kernel(kernel, Xtest, Xtrain)
     return kernel.cross_kernel(Xtest, Xtrain)

@@ -25,6 +25,8 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 
+#include "launchers.h"
+
 typedef __attribute__((ext_vector_type(4))) double f64x4;
 
 #define DB 64          // diagonal / tile block edge

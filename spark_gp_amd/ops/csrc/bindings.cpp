@@ -4,75 +4,12 @@
 #include <hip/hip_runtime.h>
 #include <c10/hip/HIPStream.h>
 
+#include <climits>
+#include <initializer_list>
 #include <vector>
 
 #include "kernel_geom.h"
-
-extern "C" hipError_t launch_fused_expert_nll(
-    const float* X, const float* y, const float* scale, float amp,
-    float noise, int E, int k, int d, double* out_nll, double* out_sumW0,
-    double* out_trG, double* out_contr, int* out_bad,
-    unsigned long long* out_clk, hipStream_t stream, size_t* lds_used);
-
-extern "C" hipError_t launch_cross_kernel_tile(
-    const float* X, const float* A, const float* s2v, float amp, int c,
-    int m, int d, void* out, void* out_lo, void* out_t, void* out_lo_t,
-    int out_is_bf16, const float* yv, double* Ky, hipStream_t stream);
-
-extern "C" hipError_t launch_syrk_bf16(const void* KcT, const void* KlT,
-                                       int c, int m, int cpitch, int split_k,
-                                       float* KK, hipStream_t stream);
-
-extern "C" hipError_t launch_syrk_bf16_sync(const void* KcT, const void* KlT,
-                                            int c, int m, int cpitch,
-                                            const int* tiles, int nb,
-                                            int kpb, int* phase_ctr,
-                                            int nactive, float* KK,
-                                            hipStream_t stream);
-
-extern "C" hipError_t launch_cross_mfma(const float* Xs, const float* As,
-                                         const float* nx, const float* na,
-                                         float amp, int c, int m, int d,
-                                         void* out_bfT, void* out_loT,
-                                         const float* yv, double* Ky,
-                                         hipStream_t stream);
-
-extern "C" hipError_t launch_syrk_fused_gen(
-    const float* Xs, const float* As, const float* nx, const float* na,
-    float amp, const float* yv, int c, int m, int d, int split_k,
-    double* Ky, float* KK, hipStream_t stream);
-
-extern "C" hipError_t launch_colsum_gemv(const void* Kc, const float* y,
-                                         int c, int m, double* Ky,
-                                         hipStream_t stream);
-
-extern "C" hipError_t launch_fused_laplace_evidence(
-    const float* X, const float* y, float* f, const float* scale, float amp,
-    float noise, int E, int k, int d, double tol, int max_newton,
-    double* out_psi, double* out_sumlogl, int* out_iters, int* out_bad,
-    double* out_logz, double* out_grad, hipStream_t stream,
-    size_t* lds_used);
-
-extern "C" hipError_t launch_synth_regression(float* X, float* y, long n,
-                                              int d, unsigned long long seed,
-                                              float noise_sd,
-                                              hipStream_t stream);
-
-extern "C" hipError_t launch_dpotrf_diag(double* A, long m, int jb,
-                                         double* Vout, int* bad,
-                                         hipStream_t stream);
-
-extern "C" hipError_t launch_dgemm64(int ta, int tb, int sub, int syrk,
-                                     const double* A, const double* B,
-                                     double* C, int M, int N, int K,
-                                     long lda, long ldb, long ldc,
-                                     hipStream_t stream);
-
-extern "C" hipError_t launch_fused_laplace_newton(
-    const float* X, const float* y, float* f, const float* scale, float amp,
-    float noise, int E, int k, int d, double tol, int max_newton,
-    double* out_psi, double* out_sumlogl, int* out_iters, int* out_bad,
-    hipStream_t stream, size_t* lds_used);
+#include "launchers.h"
 
 namespace {
 
@@ -84,6 +21,74 @@ hipStream_t current_stream() {
   return c10::hip::getCurrentHIPStream().stream();
 }
 
+// ---- argument validation --------------------------------------------------
+// Every binding checks dtype, rank and shape of each argument first (tensor
+// metadata only, so these also work on CPU tensors) and the devices last,
+// before anything is allocated or launched.
+
+constexpr int64_t ANY = -1;   // a free size in check_arg
+constexpr auto F32 = torch::kFloat32, F64 = torch::kFloat64;
+constexpr auto BF16 = torch::kBFloat16, I32 = torch::kInt32;
+
+void check_dtype(const torch::Tensor& t, const char* name,
+                 torch::ScalarType dtype, bool in_place) {
+  TORCH_CHECK(t.scalar_type() == dtype, name, " must be ", dtype, ", got ",
+              t.scalar_type());
+  // a kernel cannot write through a contiguous copy
+  TORCH_CHECK(!in_place || t.is_contiguous(), name, " must be contiguous");
+}
+
+void check_arg(const torch::Tensor& t, const char* name,
+               torch::ScalarType dtype, std::initializer_list<int64_t> sizes,
+               bool in_place = false) {
+  check_dtype(t, name, dtype, in_place);
+  bool ok = t.dim() == (int64_t)sizes.size();
+  for (size_t i = 0; ok && i < sizes.size(); ++i)
+    ok = sizes.begin()[i] == ANY || t.size(i) == sizes.begin()[i];
+  TORCH_CHECK(ok, name, " must have shape ", c10::IntArrayRef(sizes),
+              " (-1: any), got ", t.sizes());
+}
+
+// a vector of n elements of any rank ([n], [n, 1], ...)
+void check_vec(const torch::Tensor& t, const char* name,
+               torch::ScalarType dtype, int64_t n, bool in_place = false) {
+  check_dtype(t, name, dtype, in_place);
+  TORCH_CHECK(t.numel() == n, name, " must have ", n, " elements, got ",
+              t.numel());
+}
+
+struct Arg {
+  const torch::Tensor* t;   // null: an absent optional argument
+  const char* name;
+};
+
+// Every tensor is on a GPU, and all on the same one.
+void check_same_gpu(std::initializer_list<Arg> args) {
+  const Arg* first = nullptr;
+  for (const Arg& a : args) {
+    if (!a.t) continue;
+    TORCH_CHECK(a.t->is_cuda(), a.name, " must be on the GPU, got ",
+                a.t->device());
+    if (!first) first = &a;
+    TORCH_CHECK(a.t->device() == first->t->device(), a.name, " is on ",
+                a.t->device(), " but ", first->name, " is on ",
+                first->t->device());
+  }
+}
+
+void* ptr_or_null(const torch::Tensor& t) {
+  return t.defined() ? t.data_ptr() : nullptr;
+}
+
+// kernels take dense inputs: replace each by its contiguous form
+void make_contiguous(std::initializer_list<torch::Tensor*> ts) {
+  for (torch::Tensor* t : ts) *t = t->contiguous();
+}
+
+torch::TensorOptions like(const torch::Tensor& t, torch::ScalarType dtype) {
+  return torch::TensorOptions().dtype(dtype).device(t.device());
+}
+
 }  // namespace
 
 // Returns (nll[E] f64, sumW0[E] f64, trG[E] f64, contr[E,d] f64, bad[E] i32)
@@ -92,38 +97,30 @@ std::vector<torch::Tensor> fused_expert_nll_impl(torch::Tensor X,
                                                  torch::Tensor scale,
                                                  double amp, double noise,
                                                  bool profile) {
-  TORCH_CHECK(X.is_cuda() && X.dtype() == torch::kFloat32 && X.dim() == 3,
-              "X must be [E, k, d] float32 on GPU");
-  TORCH_CHECK(y.is_cuda() && y.dtype() == torch::kFloat32 && y.dim() == 2);
-  TORCH_CHECK(scale.is_cuda() && scale.dtype() == torch::kFloat32);
-  auto Xc = X.contiguous();
-  auto yc = y.contiguous();
-  auto sc = scale.contiguous();
+  check_arg(X, "X", F32, {ANY, ANY, ANY});
   const int E = X.size(0), k = X.size(1), d = X.size(2);
-  TORCH_CHECK(k <= 128 && d <= 128,
-              "fused_expert_nll requires k<=128, d<=128");
-  auto opts64 = torch::TensorOptions().dtype(torch::kFloat64).device(X.device());
-  auto opts32i = torch::TensorOptions().dtype(torch::kInt32).device(X.device());
-  auto nll = torch::empty({E}, opts64);
-  auto sumW0 = torch::empty({E}, opts64);
-  auto trG = torch::empty({E}, opts64);
-  auto contr = torch::empty({E, d}, opts64);
-  auto bad = torch::empty({E}, opts32i);
+  check_arg(y, "y", F32, {E, k});
+  check_vec(scale, "scale", F32, d);
+  TORCH_CHECK(k <= 128 && d <= 128, "X must be [E, k, d] with k<=128, "
+              "d<=128 for fused_expert_nll, got ", X.sizes());
+  check_same_gpu({{&X, "X"}, {&y, "y"}, {&scale, "scale"}});
+  make_contiguous({&X, &y, &scale});
+  auto nll = torch::empty({E}, like(X, F64));
+  auto sumW0 = torch::empty_like(nll), trG = torch::empty_like(nll);
+  auto contr = torch::empty({E, d}, like(X, F64));
+  auto bad = torch::empty({E}, like(X, I32));
   torch::Tensor clk;
   unsigned long long* clk_ptr = nullptr;
   if (profile) {
-    clk = torch::zeros({E, 20},
-                       torch::TensorOptions().dtype(torch::kInt64)
-                           .device(X.device()));
+    clk = torch::zeros({E, 20}, like(X, torch::kInt64));
     clk_ptr = (unsigned long long*)clk.data_ptr<int64_t>();
   }
-  size_t lds = 0;
   check_hip(launch_fused_expert_nll(
-                Xc.data_ptr<float>(), yc.data_ptr<float>(),
-                sc.data_ptr<float>(), (float)amp, (float)noise, E, k, d,
+                X.data_ptr<float>(), y.data_ptr<float>(),
+                scale.data_ptr<float>(), (float)amp, (float)noise, E, k, d,
                 nll.data_ptr<double>(), sumW0.data_ptr<double>(),
                 trG.data_ptr<double>(), contr.data_ptr<double>(),
-                bad.data_ptr<int>(), clk_ptr, current_stream(), &lds),
+                bad.data_ptr<int>(), clk_ptr, current_stream()),
             "fused_expert_nll");
   if (profile) return {nll, sumW0, trG, contr, bad, clk};
   return {nll, sumW0, trG, contr, bad};
@@ -140,71 +137,57 @@ bool fused_expert_nll_supported(int64_t k, int64_t d) {
   return nll_lds_bytes((int)k, (int)d) <= GEOM_LDS_MAX;
 }
 
-std::vector<torch::Tensor> cross_kernel_tile(torch::Tensor X, torch::Tensor A,
-                                             torch::Tensor s2v, double amp,
-                                             bool bf16_out, bool hilo,
-                                             bool want_t) {
-  TORCH_CHECK(X.is_cuda() && X.dtype() == torch::kFloat32 && X.dim() == 2);
-  TORCH_CHECK(A.is_cuda() && A.dtype() == torch::kFloat32 && A.dim() == 2);
-  TORCH_CHECK(X.size(1) == A.size(1), "feature dims differ");
-  TORCH_CHECK(!hilo || bf16_out, "hilo requires bf16 output");
-  TORCH_CHECK(!want_t || hilo, "transposed outputs require hilo bf16 mode");
-  auto Xc = X.contiguous();
-  auto Ac = A.contiguous();
-  auto sc = s2v.contiguous();
-  const int c = X.size(0), m = A.size(0), d = X.size(1);
-  auto opts = torch::TensorOptions()
-                  .dtype(bf16_out ? torch::kBFloat16 : torch::kFloat32)
-                  .device(X.device());
-  auto out = torch::empty({c, m}, opts);
-  torch::Tensor lo, outT, loT;
-  if (hilo) lo = torch::empty({c, m}, opts);
+// The elementwise RBF/ARD tile in both of its uses.  want_cm: write the
+// [c, m] copies (hi, and lo with hilo); want_t: write the transposed hi/lo
+// pair; y/Ky (both or neither): also accumulate Ky += K^T y from the fp32
+// register values.  Returns the tensors written, in the order
+// (out, lo, outT, loT).
+static std::vector<torch::Tensor> cross_tile(
+    const char* what, torch::Tensor X, torch::Tensor A, torch::Tensor s2v,
+    double amp, bool bf16_out, bool want_cm, bool hilo, bool want_t,
+    torch::Tensor* y, const torch::Tensor* Ky) {
+  check_arg(X, "X", F32, {ANY, ANY});
+  const int c = X.size(0), d = X.size(1);
+  check_arg(A, "A", F32, {ANY, d});
+  const int m = A.size(0);
+  check_vec(s2v, "s2v", F32, d);
+  if (y) {
+    check_vec(*y, "y", F32, c);
+    check_vec(*Ky, "Ky", F64, m, true);
+  }
+  check_same_gpu({{&X, "X"}, {&A, "A"}, {&s2v, "s2v"}, {y, "y"}, {Ky, "Ky"}});
+  make_contiguous({&X, &A, &s2v});
+  if (y) make_contiguous({y});
+  auto opts = like(X, bf16_out ? BF16 : F32);
+  torch::Tensor out, lo, outT, loT;
+  if (want_cm) out = torch::empty({c, m}, opts);
+  if (want_cm && hilo) lo = torch::empty({c, m}, opts);
   if (want_t) {
     outT = torch::empty({m, c}, opts);
     loT = torch::empty({m, c}, opts);
   }
-  check_hip(launch_cross_kernel_tile(Xc.data_ptr<float>(), Ac.data_ptr<float>(),
-                                     sc.data_ptr<float>(), (float)amp, c, m, d,
-                                     out.data_ptr(),
-                                     hilo ? lo.data_ptr() : nullptr,
-                                     want_t ? outT.data_ptr() : nullptr,
-                                     want_t ? loT.data_ptr() : nullptr,
-                                     bf16_out ? 1 : 0, nullptr, nullptr,
-                                     current_stream()),
-            "cross_kernel_tile");
-  if (want_t) return {out, lo, outT, loT};
-  if (hilo) return {out, lo};
-  return {out};
+  check_hip(launch_cross_kernel_tile(
+                X.data_ptr<float>(), A.data_ptr<float>(),
+                s2v.data_ptr<float>(), (float)amp, c, m, d, ptr_or_null(out),
+                ptr_or_null(lo), ptr_or_null(outT), ptr_or_null(loT),
+                bf16_out ? 1 : 0,
+                y ? y->data_ptr<float>() : nullptr,
+                y ? Ky->data_ptr<double>() : nullptr, current_stream()),
+            what);
+  std::vector<torch::Tensor> res;
+  for (const auto& t : {out, lo, outT, loT})
+    if (t.defined()) res.push_back(t);
+  return res;
 }
 
-// MFMA PPA tile: pre-scaled inputs + norms; K1's sqdist-via-GEMM plan.
-std::vector<torch::Tensor> cross_mfma_ppa(torch::Tensor Xs, torch::Tensor As,
-                                          torch::Tensor nx, torch::Tensor na,
-                                          double amp, torch::Tensor y,
-                                          torch::Tensor Ky) {
-  TORCH_CHECK(Xs.is_cuda() && Xs.dtype() == torch::kFloat32 && Xs.dim() == 2);
-  TORCH_CHECK(As.is_cuda() && As.dtype() == torch::kFloat32 && As.dim() == 2);
-  TORCH_CHECK(Xs.size(1) == As.size(1));
-  const int c = Xs.size(0), m = As.size(0), d = Xs.size(1);
-  TORCH_CHECK(nx.numel() == c && na.numel() == m && y.numel() == c);
-  TORCH_CHECK(Ky.is_cuda() && Ky.dtype() == torch::kFloat64 &&
-              Ky.numel() == m);
-  auto Xc = Xs.contiguous();
-  auto Ac = As.contiguous();
-  auto nxc = nx.contiguous();
-  auto nac = na.contiguous();
-  auto yc = y.contiguous();
-  auto opts = torch::TensorOptions().dtype(torch::kBFloat16)
-                  .device(Xs.device());
-  auto outT = torch::empty({m, c}, opts);
-  auto loT = torch::empty({m, c}, opts);
-  check_hip(launch_cross_mfma(Xc.data_ptr<float>(), Ac.data_ptr<float>(),
-                              nxc.data_ptr<float>(), nac.data_ptr<float>(),
-                              (float)amp, c, m, d, outT.data_ptr(),
-                              loT.data_ptr(), yc.data_ptr<float>(),
-                              Ky.data_ptr<double>(), current_stream()),
-            "cross_mfma_ppa");
-  return {outT, loT};
+std::vector<torch::Tensor> cross_kernel_tile(torch::Tensor X, torch::Tensor A,
+                                             torch::Tensor s2v, double amp,
+                                             bool bf16_out, bool hilo,
+                                             bool want_t) {
+  TORCH_CHECK(!hilo || bf16_out, "hilo requires bf16 output");
+  TORCH_CHECK(!want_t || hilo, "transposed outputs require hilo bf16 mode");
+  return cross_tile("cross_kernel_tile", X, A, s2v, amp, bf16_out, true, hilo,
+                    want_t, nullptr, nullptr);
 }
 
 // PPA fast path: transposed hi/lo tiles ONLY (no [c, m] copies written)
@@ -215,84 +198,95 @@ std::vector<torch::Tensor> cross_kernel_tile_ppa(torch::Tensor X,
                                                  torch::Tensor s2v,
                                                  double amp, torch::Tensor y,
                                                  torch::Tensor Ky) {
-  TORCH_CHECK(X.is_cuda() && X.dtype() == torch::kFloat32 && X.dim() == 2);
-  TORCH_CHECK(A.is_cuda() && A.dtype() == torch::kFloat32 && A.dim() == 2);
-  TORCH_CHECK(X.size(1) == A.size(1), "feature dims differ");
-  TORCH_CHECK(y.is_cuda() && y.dtype() == torch::kFloat32 &&
-              y.numel() == X.size(0));
-  TORCH_CHECK(Ky.is_cuda() && Ky.dtype() == torch::kFloat64 &&
-              Ky.numel() == A.size(0));
-  auto Xc = X.contiguous();
-  auto Ac = A.contiguous();
-  auto sc = s2v.contiguous();
-  auto yc = y.contiguous();
-  const int c = X.size(0), m = A.size(0), d = X.size(1);
-  auto opts = torch::TensorOptions().dtype(torch::kBFloat16)
-                  .device(X.device());
-  auto outT = torch::empty({m, c}, opts);
-  auto loT = torch::empty({m, c}, opts);
-  check_hip(launch_cross_kernel_tile(Xc.data_ptr<float>(), Ac.data_ptr<float>(),
-                                     sc.data_ptr<float>(), (float)amp, c, m, d,
-                                     nullptr, nullptr, outT.data_ptr(),
-                                     loT.data_ptr(), 1,
-                                     yc.data_ptr<float>(),
-                                     Ky.data_ptr<double>(), current_stream()),
-            "cross_kernel_tile_ppa");
+  return cross_tile("cross_kernel_tile_ppa", X, A, s2v, amp, true, false,
+                    true, true, &y, &Ky);
+}
+
+// Shapes of the pre-scaled PPA inputs shared by cross_mfma_ppa and
+// ppa_fused_acc: Xs [c, d], As [m, d], their squared norms, y and Ky.
+static void check_ppa_inputs(const torch::Tensor& Xs, const torch::Tensor& As,
+                             const torch::Tensor& nx, const torch::Tensor& na,
+                             const torch::Tensor& y, const torch::Tensor& Ky) {
+  check_arg(Xs, "Xs", F32, {ANY, ANY});
+  check_arg(As, "As", F32, {ANY, Xs.size(1)});
+  check_vec(nx, "nx", F32, Xs.size(0));
+  check_vec(na, "na", F32, As.size(0));
+  check_vec(y, "y", F32, Xs.size(0));
+  check_vec(Ky, "Ky", F64, As.size(0), true);
+}
+
+// MFMA PPA tile: pre-scaled inputs + norms; K1's sqdist-via-GEMM plan.
+std::vector<torch::Tensor> cross_mfma_ppa(torch::Tensor Xs, torch::Tensor As,
+                                          torch::Tensor nx, torch::Tensor na,
+                                          double amp, torch::Tensor y,
+                                          torch::Tensor Ky) {
+  check_ppa_inputs(Xs, As, nx, na, y, Ky);
+  check_same_gpu({{&Xs, "Xs"}, {&As, "As"}, {&nx, "nx"}, {&na, "na"},
+                  {&y, "y"}, {&Ky, "Ky"}});
+  const int c = Xs.size(0), m = As.size(0), d = Xs.size(1);
+  make_contiguous({&Xs, &As, &nx, &na, &y});
+  auto outT = torch::empty({m, c}, like(Xs, BF16));
+  auto loT = torch::empty_like(outT);
+  check_hip(launch_cross_mfma(Xs.data_ptr<float>(), As.data_ptr<float>(),
+                              nx.data_ptr<float>(), na.data_ptr<float>(),
+                              (float)amp, c, m, d, outT.data_ptr(),
+                              loT.data_ptr(), y.data_ptr<float>(),
+                              Ky.data_ptr<double>(), current_stream()),
+            "cross_mfma_ppa");
   return {outT, loT};
 }
 
-// KcT/KlT are the TRANSPOSED kernel blocks [m, c] (k along the contiguous
-// axis; see syrk_bf16_kernel).  KK [m, m] is accumulated in place.
+// Checked, contiguous operands of the two SYRK wrappers: KcT/KlT are the
+// TRANSPOSED kernel blocks [m, c] (k along the contiguous axis; see
+// syrk_bf16_kernel; the second is undefined without KlT), KK [m, m] is
+// accumulated in place.  `more`: the wrapper's further tensor, if any.
+static std::pair<torch::Tensor, torch::Tensor> syrk_operands(
+    const torch::Tensor& KcT, const c10::optional<torch::Tensor>& KlT,
+    const torch::Tensor& KK, Arg more = {nullptr, ""}) {
+  check_arg(KcT, "KcT", BF16, {ANY, ANY});
+  const int64_t m = KcT.size(0), c = KcT.size(1);
+  if (KlT.has_value()) check_arg(*KlT, "KlT", BF16, {m, c});
+  check_arg(KK, "KK", F32, {m, m}, true);   // m = KcT.size(0)
+  check_same_gpu({{&KcT, "KcT"}, {KlT.has_value() ? &*KlT : nullptr, "KlT"},
+                  {&KK, "KK"}, more});
+  return {KcT.contiguous(),
+          KlT.has_value() ? KlT->contiguous() : torch::Tensor()};
+}
+
 void syrk_bf16_acc(torch::Tensor KcT, c10::optional<torch::Tensor> KlT,
                    torch::Tensor KK, int64_t split_k) {
-  TORCH_CHECK(KcT.is_cuda() && KcT.dtype() == torch::kBFloat16 &&
-              KcT.dim() == 2);
-  TORCH_CHECK(KK.is_cuda() && KK.dtype() == torch::kFloat32 && KK.dim() == 2);
-  auto Kcc = KcT.contiguous();
-  const int m = KcT.size(0), c = KcT.size(1);
-  TORCH_CHECK(KK.size(0) == m && KK.size(1) == m,
-              "KK must be [m, m] with m = KcT.size(0) (transposed operand)");
-  torch::Tensor Klc;
-  if (KlT.has_value()) {
-    TORCH_CHECK(KlT->sizes() == KcT.sizes() &&
-                KlT->dtype() == torch::kBFloat16);
-    Klc = KlT->contiguous();
-  }
-  check_hip(launch_syrk_bf16(Kcc.data_ptr(),
-                             KlT.has_value() ? Klc.data_ptr() : nullptr, c, m,
-                             c, (int)split_k, KK.data_ptr<float>(),
+  TORCH_CHECK(split_k >= 1 && split_k <= 65535,   // becomes gridDim.y
+              "split_k out of range [1, 65535]: ", split_k);
+  auto [Kc, Kl] = syrk_operands(KcT, KlT, KK);
+  const int m = Kc.size(0), c = Kc.size(1);
+  check_hip(launch_syrk_bf16(Kc.data_ptr(), ptr_or_null(Kl), c, m, c,
+                             (int)split_k, KK.data_ptr<float>(),
                              current_stream()),
             "syrk_bf16");
 }
 
 // k-synchronized SYRK (large m): tiles [nb, 2] int32 (ti, tj; -1 pads),
 // one block per tile, accumulators held across all k; see cross_syrk.hip.
+// Only the shape of `tiles` is checked: reading its contents would
+// synchronise with the device.  They stay trusted — ppa_plan's
+// syrk_sync_tile_lists is the only producer.
 void syrk_bf16_sync_acc(torch::Tensor KcT, c10::optional<torch::Tensor> KlT,
                         torch::Tensor KK, torch::Tensor tiles,
                         int64_t kpb, int64_t nactive) {
-  TORCH_CHECK(KcT.is_cuda() && KcT.dtype() == torch::kBFloat16 &&
-              KcT.dim() == 2 && KcT.is_contiguous());
-  TORCH_CHECK(KK.is_cuda() && KK.dtype() == torch::kFloat32 && KK.dim() == 2);
-  TORCH_CHECK(tiles.is_cuda() && tiles.dtype() == torch::kInt32 &&
-              tiles.dim() == 2 && tiles.size(1) == 2 && tiles.is_contiguous());
-  const int m = KcT.size(0), c = KcT.size(1);
-  TORCH_CHECK(KK.size(0) == m && KK.size(1) == m);
-  torch::Tensor Klc;
-  if (KlT.has_value()) {
-    TORCH_CHECK(KlT->sizes() == KcT.sizes() &&
-                KlT->dtype() == torch::kBFloat16);
-    Klc = KlT->contiguous();
-  }
+  check_arg(tiles, "tiles", I32, {ANY, 2}, true);
+  TORCH_CHECK(kpb >= 1 && kpb <= INT_MAX, "kpb must be >= 1, got ", kpb);
+  TORCH_CHECK(nactive >= 0 && nactive <= tiles.size(0),
+              "nactive out of range [0, tiles.size(0) = ", tiles.size(0),
+              "]: ", nactive);
+  auto [Kc, Kl] = syrk_operands(KcT, KlT, KK, {&tiles, "tiles"});
+  const int m = Kc.size(0), c = Kc.size(1);
   const int kblocks = (c + SY_BK - 1) / SY_BK;
   const int nphases = (kblocks + (int)kpb - 1) / (int)kpb;
-  auto ctr = torch::zeros({nphases},
-                          torch::TensorOptions().dtype(torch::kInt32)
-                              .device(KK.device()));
+  auto ctr = torch::zeros({nphases}, like(KK, I32));
   check_hip(launch_syrk_bf16_sync(
-                KcT.data_ptr(), KlT.has_value() ? Klc.data_ptr() : nullptr,
-                c, m, c, tiles.data_ptr<int>(), (int)tiles.size(0),
-                (int)kpb, ctr.data_ptr<int>(), (int)nactive,
-                KK.data_ptr<float>(), current_stream()),
+                Kc.data_ptr(), ptr_or_null(Kl), c, m, c, tiles.data_ptr<int>(),
+                (int)tiles.size(0), (int)kpb, ctr.data_ptr<int>(),
+                (int)nactive, KK.data_ptr<float>(), current_stream()),
             "syrk_bf16_sync");
 }
 
@@ -302,137 +296,95 @@ void syrk_bf16_sync_acc(torch::Tensor KcT, c10::optional<torch::Tensor> KlT,
 bool ppa_fused_supported(int64_t m, int64_t d) {
   if (m < 1 || d < 1 || d > SF_DMAX) return false;
   const int64_t ntile = (m + SY_CT - 1) / SY_CT;
-  return ntile * (ntile + 1) / 2 <= 256;  // larger tile sets: sync kernel
+  return ntile * (ntile + 1) / 2 <= SY_SPLITK_MAX_TILES;
 }
 
 void ppa_fused_acc(torch::Tensor Xs, torch::Tensor As, torch::Tensor nx,
                    torch::Tensor na, double amp, torch::Tensor y,
                    torch::Tensor Ky, torch::Tensor KK, int64_t split_k) {
-  TORCH_CHECK(Xs.is_cuda() && Xs.dtype() == torch::kFloat32 && Xs.dim() == 2);
-  TORCH_CHECK(As.is_cuda() && As.dtype() == torch::kFloat32 && As.dim() == 2);
-  TORCH_CHECK(Xs.size(1) == As.size(1));
+  check_ppa_inputs(Xs, As, nx, na, y, Ky);
   const int c = Xs.size(0), m = As.size(0), d = Xs.size(1);
-  TORCH_CHECK(ppa_fused_supported(m, d),
-              "ppa_fused_acc: unsupported (m, d); query ppa_fused_supported");
-  TORCH_CHECK(nx.is_cuda() && nx.dtype() == torch::kFloat32 &&
-              nx.numel() == c);
-  TORCH_CHECK(na.is_cuda() && na.dtype() == torch::kFloat32 &&
-              na.numel() == m);
-  TORCH_CHECK(y.is_cuda() && y.dtype() == torch::kFloat32 && y.numel() == c);
-  TORCH_CHECK(Ky.is_cuda() && Ky.dtype() == torch::kFloat64 &&
-              Ky.numel() == m && Ky.is_contiguous());
-  TORCH_CHECK(KK.is_cuda() && KK.dtype() == torch::kFloat32 &&
-              KK.dim() == 2 && KK.size(0) == m && KK.size(1) == m &&
-              KK.is_contiguous());
-  TORCH_CHECK(split_k >= 1 && split_k <= 65535, "split_k out of range");
+  TORCH_CHECK(ppa_fused_supported(m, d), "As: unsupported (m, d) for "
+              "ppa_fused_acc; query ppa_fused_supported");
+  check_arg(KK, "KK", F32, {m, m}, true);
+  TORCH_CHECK(split_k >= 1 && split_k <= 65535,
+              "split_k out of range [1, 65535]: ", split_k);
+  check_same_gpu({{&Xs, "Xs"}, {&As, "As"}, {&nx, "nx"}, {&na, "na"},
+                  {&y, "y"}, {&Ky, "Ky"}, {&KK, "KK"}});
   if (c == 0) return;
-  auto Xc = Xs.contiguous();
-  auto Ac = As.contiguous();
-  auto nxc = nx.contiguous();
-  auto nac = na.contiguous();
-  auto yc = y.contiguous();
+  make_contiguous({&Xs, &As, &nx, &na, &y});
   check_hip(launch_syrk_fused_gen(
-                Xc.data_ptr<float>(), Ac.data_ptr<float>(),
-                nxc.data_ptr<float>(), nac.data_ptr<float>(), (float)amp,
-                yc.data_ptr<float>(), c, m, d, (int)split_k,
+                Xs.data_ptr<float>(), As.data_ptr<float>(),
+                nx.data_ptr<float>(), na.data_ptr<float>(), (float)amp,
+                y.data_ptr<float>(), c, m, d, (int)split_k,
                 Ky.data_ptr<double>(), KK.data_ptr<float>(),
                 current_stream()),
             "ppa_fused_acc");
 }
 
 void colsum_gemv_acc(torch::Tensor Kc, torch::Tensor y, torch::Tensor Ky) {
-  TORCH_CHECK(Kc.is_cuda() && Kc.dtype() == torch::kBFloat16 && Kc.dim() == 2);
-  TORCH_CHECK(y.is_cuda() && y.dtype() == torch::kFloat32);
-  TORCH_CHECK(Ky.is_cuda() && Ky.dtype() == torch::kFloat64);
-  auto Kcc = Kc.contiguous();
+  check_arg(Kc, "Kc", BF16, {ANY, ANY});
   const int c = Kc.size(0), m = Kc.size(1);
-  check_hip(launch_colsum_gemv(Kcc.data_ptr(), y.contiguous().data_ptr<float>(),
-                               c, m, Ky.data_ptr<double>(), current_stream()),
+  check_vec(y, "y", F32, c);
+  check_vec(Ky, "Ky", F64, m, true);
+  check_same_gpu({{&Kc, "Kc"}, {&y, "y"}, {&Ky, "Ky"}});
+  make_contiguous({&Kc, &y});
+  check_hip(launch_colsum_gemv(Kc.data_ptr(), y.data_ptr<float>(), c, m,
+                               Ky.data_ptr<double>(), current_stream()),
             "colsum_gemv");
 }
 
-// Runs the per-expert Laplace Newton loop in place on f.
-// Returns (psi[E] f64, sumlogl[E] f64, iters[E] i32, bad[E] i32).
-std::vector<torch::Tensor> fused_laplace_newton(torch::Tensor X,
-                                                torch::Tensor y,
-                                                torch::Tensor f,
-                                                torch::Tensor scale,
-                                                double amp, double noise,
-                                                double tol,
-                                                int64_t max_newton) {
-  TORCH_CHECK(X.is_cuda() && X.dtype() == torch::kFloat32 && X.dim() == 3);
-  TORCH_CHECK(y.is_cuda() && y.dtype() == torch::kFloat32 && y.dim() == 2);
-  TORCH_CHECK(f.is_cuda() && f.dtype() == torch::kFloat32 && f.dim() == 2
-              && f.is_contiguous(), "f must be contiguous fp32 (updated "
-              "in place)");
-  auto Xc = X.contiguous();
-  auto yc = y.contiguous();
-  auto sc = scale.contiguous();
+// The per-expert Laplace Newton loop, run in place on f.
+// EV = false: returns (psi[E] f64, sumlogl[E] f64, iters[E] i32, bad[E] i32).
+// EV = true: fused Newton + Algorithm 5.1 evidence/gradient (K11) — the
+// evidence pass follows in the same launch; returns (logz[E] f64,
+// grad[E, d+2] f64 — beta grads then amp then noise, all d(logZ)/d(theta)
+// un-negated —, iters[E] i32, bad[E] i32).
+template <bool EV>
+std::vector<torch::Tensor> fused_laplace(torch::Tensor X, torch::Tensor y,
+                                         torch::Tensor f, torch::Tensor scale,
+                                         double amp, double noise, double tol,
+                                         int64_t max_newton) {
+  const char* what = EV ? "fused_laplace_evidence" : "fused_laplace_newton";
+  check_arg(X, "X", F32, {ANY, ANY, ANY});
   const int E = X.size(0), k = X.size(1), d = X.size(2);
-  TORCH_CHECK(k <= 128 && d <= k,
-              "fused_laplace_newton requires k<=128, d<=k");
-  auto opts64 = torch::TensorOptions().dtype(torch::kFloat64).device(X.device());
-  auto opts32i = torch::TensorOptions().dtype(torch::kInt32).device(X.device());
-  auto psi = torch::empty({E}, opts64);
-  auto sll = torch::empty({E}, opts64);
-  auto iters = torch::empty({E}, opts32i);
-  auto bad = torch::empty({E}, opts32i);
-  size_t lds = 0;
-  check_hip(launch_fused_laplace_newton(
-                Xc.data_ptr<float>(), yc.data_ptr<float>(),
-                f.data_ptr<float>(), sc.data_ptr<float>(), (float)amp,
+  check_arg(y, "y", F32, {E, k});
+  check_arg(f, "f", F32, {E, k}, true);   // updated in place
+  check_vec(scale, "scale", F32, d);
+  TORCH_CHECK(k <= 128 && d <= k, "X must be [E, k, d] with k<=128, d<=k "
+              "for ", what, ", got ", X.sizes());
+  check_same_gpu({{&X, "X"}, {&y, "y"}, {&f, "f"}, {&scale, "scale"}});
+  make_contiguous({&X, &y, &scale});
+  auto psi = torch::empty({E}, like(X, F64)), sll = torch::empty_like(psi);
+  auto iters = torch::empty({E}, like(X, I32)), bad = torch::empty_like(iters);
+  if (!EV) {
+    check_hip(launch_fused_laplace_newton(
+                  X.data_ptr<float>(), y.data_ptr<float>(),
+                  f.data_ptr<float>(), scale.data_ptr<float>(), (float)amp,
+                  (float)noise, E, k, d, tol, (int)max_newton,
+                  psi.data_ptr<double>(), sll.data_ptr<double>(),
+                  iters.data_ptr<int>(), bad.data_ptr<int>(),
+                  current_stream()),
+              what);
+    return {psi, sll, iters, bad};
+  }
+  auto logz = torch::empty({E}, like(X, F64));
+  auto grad = torch::empty({E, d + 2}, like(X, F64));
+  check_hip(launch_fused_laplace_evidence(
+                X.data_ptr<float>(), y.data_ptr<float>(),
+                f.data_ptr<float>(), scale.data_ptr<float>(), (float)amp,
                 (float)noise, E, k, d, tol, (int)max_newton,
                 psi.data_ptr<double>(), sll.data_ptr<double>(),
-                iters.data_ptr<int>(), bad.data_ptr<int>(), current_stream(),
-                &lds),
-            "fused_laplace_newton");
-  return {psi, sll, iters, bad};
+                iters.data_ptr<int>(), bad.data_ptr<int>(),
+                logz.data_ptr<double>(), grad.data_ptr<double>(),
+                current_stream()),
+            what);
+  return {logz, grad, iters, bad};
 }
 
 bool fused_laplace_newton_supported(int64_t k, int64_t d) {
   if (k > 128 || d > k || k < 1) return false;
   return lap_lds_bytes((int)k, (int)d) <= GEOM_LDS_MAX;
-}
-
-// Fused Newton + Algorithm 5.1 evidence/gradient (K11).  Runs the Newton
-// loop to convergence (f updated in place), then the evidence pass in the
-// same launch.  Returns (logz[E] f64, grad[E, d+2] f64 — beta grads then
-// amp then noise, all d(logZ)/d(theta) un-negated —, iters[E] i32,
-// bad[E] i32).
-std::vector<torch::Tensor> fused_laplace_evidence(torch::Tensor X,
-                                                  torch::Tensor y,
-                                                  torch::Tensor f,
-                                                  torch::Tensor scale,
-                                                  double amp, double noise,
-                                                  double tol,
-                                                  int64_t max_newton) {
-  TORCH_CHECK(X.is_cuda() && X.dtype() == torch::kFloat32 && X.dim() == 3);
-  TORCH_CHECK(y.is_cuda() && y.dtype() == torch::kFloat32 && y.dim() == 2);
-  TORCH_CHECK(f.is_cuda() && f.dtype() == torch::kFloat32 && f.dim() == 2
-              && f.is_contiguous(), "f must be contiguous fp32");
-  auto Xc = X.contiguous();
-  auto yc = y.contiguous();
-  auto sc = scale.contiguous();
-  const int E = X.size(0), k = X.size(1), d = X.size(2);
-  auto opts64 = torch::TensorOptions().dtype(torch::kFloat64).device(X.device());
-  auto opts32i = torch::TensorOptions().dtype(torch::kInt32).device(X.device());
-  auto psi = torch::empty({E}, opts64);
-  auto sll = torch::empty({E}, opts64);
-  auto logz = torch::empty({E}, opts64);
-  auto grad = torch::empty({E, d + 2}, opts64);
-  auto iters = torch::empty({E}, opts32i);
-  auto bad = torch::empty({E}, opts32i);
-  size_t lds = 0;
-  check_hip(launch_fused_laplace_evidence(
-                Xc.data_ptr<float>(), yc.data_ptr<float>(),
-                f.data_ptr<float>(), sc.data_ptr<float>(), (float)amp,
-                (float)noise, E, k, d, tol, (int)max_newton,
-                psi.data_ptr<double>(), sll.data_ptr<double>(),
-                iters.data_ptr<int>(), bad.data_ptr<int>(),
-                logz.data_ptr<double>(), grad.data_ptr<double>(),
-                current_stream(), &lds),
-            "fused_laplace_evidence");
-  return {logz, grad, iters, bad};
 }
 
 bool fused_laplace_evidence_supported(int64_t k, int64_t d) {
@@ -449,14 +401,13 @@ bool fused_laplace_evidence_supported(int64_t k, int64_t d) {
 // explicit inverse of each diagonal block; bad (int32 [1], zeroed by the
 // caller) is set on a non-PD pivot.  mp must be a multiple of 64.
 void dpotrf64(torch::Tensor A, torch::Tensor V, torch::Tensor bad) {
-  TORCH_CHECK(A.is_cuda() && A.dtype() == torch::kFloat64 && A.dim() == 2 &&
-              A.size(0) == A.size(1) && A.is_contiguous());
-  const long mp = A.size(0);
-  TORCH_CHECK(mp % 64 == 0, "dpotrf64 requires 64-padded matrices");
-  const long nb = mp / 64;
-  TORCH_CHECK(V.is_cuda() && V.dtype() == torch::kFloat64 &&
-              V.numel() == nb * 64 * 64 && V.is_contiguous());
-  TORCH_CHECK(bad.is_cuda() && bad.dtype() == torch::kInt32);
+  check_arg(A, "A", F64, {ANY, ANY}, true);
+  const long mp = A.size(0), nb = mp / 64;
+  TORCH_CHECK(A.size(1) == mp && mp % 64 == 0,
+              "A must be square and 64-padded, got ", A.sizes());
+  check_vec(V, "V", F64, nb * 64 * 64, true);
+  check_vec(bad, "bad", I32, 1);
+  check_same_gpu({{&A, "A"}, {&V, "V"}, {&bad, "bad"}});
   auto stream = current_stream();
   double* a = A.data_ptr<double>();
   double* v = V.data_ptr<double>();
@@ -489,14 +440,13 @@ void dpotrf64(torch::Tensor A, torch::Tensor V, torch::Tensor bad) {
 // columns < (I+1)*64 — cutting the forward GEMMs from m^3 to m^3/3.
 void dchol_solve64(torch::Tensor A, torch::Tensor V, torch::Tensor B,
                    bool rhs_identity) {
-  TORCH_CHECK(A.is_cuda() && A.dtype() == torch::kFloat64 &&
-              A.is_contiguous() && A.dim() == 2);
-  TORCH_CHECK(B.is_cuda() && B.dtype() == torch::kFloat64 &&
-              B.is_contiguous() && B.dim() == 2 && B.size(0) == A.size(0));
-  const long mp = A.size(0), r = B.size(1);
-  TORCH_CHECK(mp % 64 == 0);
-  const long nb = mp / 64;
-  TORCH_CHECK(V.numel() == nb * 64 * 64);
+  check_arg(A, "A", F64, {ANY, ANY}, true);
+  const long mp = A.size(0), nb = mp / 64;
+  TORCH_CHECK(mp % 64 == 0, "A must be 64-padded, got ", A.sizes());
+  check_vec(V, "V", F64, nb * 64 * 64, true);
+  check_arg(B, "B", F64, {mp, ANY}, true);
+  check_same_gpu({{&A, "A"}, {&V, "V"}, {&B, "B"}});
+  const long r = B.size(1);
   auto stream = current_stream();
   double* a = A.data_ptr<double>();
   double* v = V.data_ptr<double>();
@@ -528,18 +478,18 @@ void dchol_solve64(torch::Tensor A, torch::Tensor V, torch::Tensor B,
 
 // Generic fp64 MFMA GEMM (layout verification + utility): C = op(A) op(B).
 torch::Tensor dgemm64(torch::Tensor A, torch::Tensor B, bool ta, bool tb) {
-  TORCH_CHECK(A.is_cuda() && A.dtype() == torch::kFloat64 && A.dim() == 2);
-  TORCH_CHECK(B.is_cuda() && B.dtype() == torch::kFloat64 && B.dim() == 2);
-  auto Ac = A.contiguous();
-  auto Bc = B.contiguous();
+  check_arg(A, "A", F64, {ANY, ANY});
+  check_arg(B, "B", F64, {ANY, ANY});
   const long M = ta ? A.size(1) : A.size(0);
   const long K = ta ? A.size(0) : A.size(1);
   const long Kb = tb ? B.size(1) : B.size(0);
   const long N = tb ? B.size(0) : B.size(1);
-  TORCH_CHECK(K == Kb, "inner dims differ");
+  TORCH_CHECK(K == Kb, "inner dims of A and B differ");
+  check_same_gpu({{&A, "A"}, {&B, "B"}});
+  make_contiguous({&A, &B});
   auto C = torch::empty({M, N}, A.options());
   check_hip(launch_dgemm64(ta ? 1 : 0, tb ? 1 : 0, 0, 0,
-                           Ac.data_ptr<double>(), Bc.data_ptr<double>(),
+                           A.data_ptr<double>(), B.data_ptr<double>(),
                            C.data_ptr<double>(), (int)M, (int)N, (int)K,
                            A.size(1), B.size(1), N, current_stream()),
             "dgemm64");
@@ -561,6 +511,11 @@ std::vector<torch::Tensor> synth_regression(int64_t n, int64_t d,
 }
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
+  // kernel geometry the Python plan module mirrors (checked by a test)
+  mod.attr("SY_CT") = (int)SY_CT;
+  mod.attr("SY_BK") = (int)SY_BK;
+  mod.attr("SF_DMAX") = (int)SF_DMAX;
+  mod.attr("SY_SPLITK_MAX_TILES") = (int)SY_SPLITK_MAX_TILES;
   mod.def("synth_regression", &synth_regression,
           "device-side Philox benchmark data (K19)");
   mod.def("dpotrf64", &dpotrf64,
@@ -570,10 +525,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
           pybind11::arg("A"), pybind11::arg("V"), pybind11::arg("B"),
           pybind11::arg("rhs_identity") = false);
   mod.def("dgemm64", &dgemm64, "fp64 MFMA GEMM (test/utility)");
-  mod.def("fused_laplace_newton", &fused_laplace_newton,
+  mod.def("fused_laplace_newton", &fused_laplace<false>,
           "per-expert Laplace Newton loop to convergence (CDNA4)");
   mod.def("fused_laplace_newton_supported", &fused_laplace_newton_supported);
-  mod.def("fused_laplace_evidence", &fused_laplace_evidence,
+  mod.def("fused_laplace_evidence", &fused_laplace<true>,
           "fused Newton + Algorithm 5.1 evidence/gradient (K11, CDNA4)");
   mod.def("fused_laplace_evidence_supported",
           &fused_laplace_evidence_supported);

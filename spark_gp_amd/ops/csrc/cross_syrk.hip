@@ -37,6 +37,7 @@
 #include <math.h>
 
 #include "kernel_geom.h"    // SY_CT, SY_BK, SF_DMAX (shared with the host)
+#include "launchers.h"
 
 typedef __bf16 bf16;
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;

@@ -55,6 +55,7 @@
 #define WG 512
 #include "linalg_lds.h"
 #include "kernel_geom.h"
+#include "launchers.h"
 
 typedef __attribute__((ext_vector_type(4))) float mfma_f32x4;
 
@@ -373,14 +374,12 @@ extern "C" hipError_t launch_fused_expert_nll(
     const float* X, const float* y, const float* scale,
     float amp, float noise, int E, int k, int d,
     double* out_nll, double* out_sumW0, double* out_trG, double* out_contr,
-    int* out_bad, unsigned long long* out_clk, hipStream_t stream,
-    size_t* lds_used) {
+    int* out_bad, unsigned long long* out_clk, hipStream_t stream) {
   size_t lds = nll_lds_bytes(k, d);
   // occupancy experiment knob: force 1 WG/CU by padding the LDS ask
   // (measures how much the usual 2 co-resident expert WGs overlap)
   if (const char* pad = getenv("SPARK_GP_AMD_NLL_LDS_PAD"))
     lds += (size_t)atol(pad);
-  if (lds_used) *lds_used = lds;
   if (lds > GEOM_LDS_MAX || k > 128 || d > 128)
     return hipErrorInvalidConfiguration;
   hipLaunchKernelGGL(fused_expert_nll_kernel, dim3(E), dim3(WG), lds, stream,

@@ -74,3 +74,6 @@ static GEOM_HD inline size_t lap_lds_bytes(int k, int d, int ev = 0) {
 #define SY_CT 256     // output tile edge (per block)
 #define SY_BK 32      // k rows per staged block
 #define SF_DMAX 32    // syrk_fused_gen: d-slots per row that fit its LDS
+// largest lower-triangle tile set the split-k family (syrk_bf16,
+// syrk_fused_gen) takes; larger sets go to the k-synchronized kernel
+#define SY_SPLITK_MAX_TILES 256

@@ -40,6 +40,7 @@
 #define WG 512
 #include "linalg_lds.h"
 #include "kernel_geom.h"
+#include "launchers.h"
 
 struct LapLds {
   float* X;     // k * dp4: raw features (16-B-aligned rows)
@@ -577,9 +578,8 @@ extern "C" hipError_t launch_fused_laplace_newton(
     const float* X, const float* y, float* f, const float* scale, float amp,
     float noise, int E, int k, int d, double tol, int max_newton,
     double* out_psi, double* out_sumlogl, int* out_iters, int* out_bad,
-    hipStream_t stream, size_t* lds_used) {
+    hipStream_t stream) {
   size_t lds = lap_lds_bytes(k, d);
-  if (lds_used) *lds_used = lds;
   if (lds > GEOM_LDS_MAX || k > 128 || d > k)
     return hipErrorInvalidConfiguration;
   hipLaunchKernelGGL(fused_laplace_kernel<false>, dim3(E), dim3(WG), lds,
@@ -593,10 +593,8 @@ extern "C" hipError_t launch_fused_laplace_evidence(
     const float* X, const float* y, float* f, const float* scale, float amp,
     float noise, int E, int k, int d, double tol, int max_newton,
     double* out_psi, double* out_sumlogl, int* out_iters, int* out_bad,
-    double* out_logz, double* out_grad, hipStream_t stream,
-    size_t* lds_used) {
+    double* out_logz, double* out_grad, hipStream_t stream) {
   size_t lds = lap_lds_bytes(k, d, 1);
-  if (lds_used) *lds_used = lds;
   if (lds > GEOM_LDS_MAX || k > 128 || d > k)
     return hipErrorInvalidConfiguration;
   hipLaunchKernelGGL(fused_laplace_kernel<true>, dim3(E), dim3(WG), lds,

@@ -11,6 +11,8 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 
+#include "launchers.h"
+
 __device__ inline void philox_round(unsigned int& c0, unsigned int& c1,
                                     unsigned int& c2, unsigned int& c3,
                                     unsigned int k0, unsigned int k1) {

@@ -9,6 +9,7 @@ interchangeable and unit-diffable.
 from __future__ import annotations
 
 import math
+import os
 from typing import Tuple
 
 import numpy as np
@@ -18,8 +19,7 @@ from ..kernels.base import Kernel
 from ..kernels.compiled import CompiledKernel, compile_kernel
 from .. import _hip_ext as ext
 from . import torch_backend
-from .ppa_gate import (ppa_fused_chunk_rows, ppa_fused_gate,
-                       ppa_fused_split_k)
+from . import ppa_plan
 
 
 def _scale_vector(cs: CompiledKernel, theta: np.ndarray, d: int,
@@ -32,13 +32,19 @@ def _scale_vector(cs: CompiledKernel, theta: np.ndarray, d: int,
     return torch.as_tensor(s, dtype=dtype, device=device)
 
 
-def supports_nll(cs: CompiledKernel, X: torch.Tensor) -> bool:
-    if cs.base not in ("ard", "rbf"):
+def _supports_expert(cs, X: torch.Tensor, kd_supported) -> bool:
+    """An RBF/ARD kernel on [E, k, d] fp32 experts whose (k, d) the fused
+    kernel's LDS budget takes (``kd_supported``: an ``ext.*_supported``)."""
+    if cs is None or cs.base not in ("ard", "rbf"):
         return False
     if X.dtype != torch.float32 or X.dim() != 3:
         return False
     E, k, d = X.shape
-    return bool(ext.fused_expert_nll_supported(k, d))
+    return bool(kd_supported(k, d))
+
+
+def supports_nll(cs: CompiledKernel, X: torch.Tensor) -> bool:
+    return _supports_expert(cs, X, ext.fused_expert_nll_supported)
 
 
 def nll_grad_compiled(cs: CompiledKernel, theta: np.ndarray,
@@ -100,18 +106,28 @@ def nll_grad_compiled(cs: CompiledKernel, theta: np.ndarray,
 # 1e-7 — BASELINE.md round 2), so the default floor matches the
 # reference's default tol.  Below it, a fp64 torch polish finishes from
 # the warm latent (see ops.__init__.laplace_nll_grad).
-import os as _os
-LAPLACE_MIN_TOL = float(_os.environ.get("SPARK_GP_AMD_LAPLACE_MIN_TOL",
-                                        "1e-6"))
+LAPLACE_MIN_TOL = float(os.environ.get("SPARK_GP_AMD_LAPLACE_MIN_TOL",
+                                       "1e-6"))
 
 
 def supports_laplace(cs: CompiledKernel, X: torch.Tensor) -> bool:
-    if cs is None or cs.base not in ("ard", "rbf"):
-        return False
-    if X.dtype != torch.float32 or X.dim() != 3:
-        return False
-    E, k, d = X.shape
-    return bool(ext.fused_laplace_newton_supported(k, d))
+    return _supports_expert(cs, X, ext.fused_laplace_newton_supported)
+
+
+def _fused_laplace(entry, cs: CompiledKernel, theta: np.ndarray,
+                   X: torch.Tensor, y: torch.Tensor, f: torch.Tensor,
+                   tol: float, max_newton: int):
+    """Call one of the two fused Laplace entry points; ``f`` is updated IN
+    PLACE.  The fused loop is a warm-starter: a torch pass finishes
+    convergence with reference semantics where needed, so the fp32
+    iterations are capped (the fp32 objective noise floor can sit above a
+    tight tol) and tol is loosened to the fp32-representable level."""
+    if not f.is_contiguous():
+        raise ValueError("latent f must be contiguous")
+    scale = _scale_vector(cs, theta, X.shape[-1], X.device)
+    return entry(X, y.to(torch.float32), f, scale, float(cs.amp(theta)),
+                 float(cs.noise(theta)), max(float(tol), LAPLACE_MIN_TOL),
+                 min(int(max_newton), 40))
 
 
 def laplace_newton(cs: CompiledKernel, theta: np.ndarray, X: torch.Tensor,
@@ -121,29 +137,13 @@ def laplace_newton(cs: CompiledKernel, theta: np.ndarray, X: torch.Tensor,
     latent ``f`` IN PLACE.  Returns the number of experts the fp32 kernel
     could not handle (their f is left unchanged; the torch evidence pass
     converges them from their warm state)."""
-    C = cs.amp(theta)
-    nu = cs.noise(theta)
-    scale = _scale_vector(cs, theta, X.shape[-1], X.device)
-    if not f.is_contiguous():
-        raise ValueError("latent f must be contiguous")
-    # The fused loop is a warm-starter: the torch evidence pass finishes
-    # convergence with reference semantics, so cap the fp32 iterations (the
-    # fp32 objective noise floor can sit above a tight tol) and loosen tol
-    # to the fp32-representable level.
-    eff_tol = max(float(tol), LAPLACE_MIN_TOL)
-    psi, sll, iters, bad = ext.fused_laplace_newton(
-        X, y.to(torch.float32), f, scale, float(C), float(nu), eff_tol,
-        min(int(max_newton), 40))
+    psi, sll, iters, bad = _fused_laplace(ext.fused_laplace_newton, cs, theta,
+                                          X, y, f, tol, max_newton)
     return int((bad != 0).sum())
 
 
 def supports_laplace_evidence(cs: CompiledKernel, X: torch.Tensor) -> bool:
-    if cs is None or cs.base not in ("ard", "rbf"):
-        return False
-    if X.dtype != torch.float32 or X.dim() != 3:
-        return False
-    E, k, d = X.shape
-    return bool(ext.fused_laplace_evidence_supported(k, d))
+    return _supports_expert(cs, X, ext.fused_laplace_evidence_supported)
 
 
 def laplace_evidence(cs: CompiledKernel, theta: np.ndarray, X: torch.Tensor,
@@ -154,16 +154,9 @@ def laplace_evidence(cs: CompiledKernel, theta: np.ndarray, X: torch.Tensor,
     f in place.  Returns (nll, grad) with the torch-path sign convention,
     or None when any expert's fp32 factor broke down (caller falls back
     to the warm torch Newton)."""
-    C = cs.amp(theta)
-    nu = cs.noise(theta)
     d = X.shape[-1]
-    scale = _scale_vector(cs, theta, d, X.device)
-    if not f.is_contiguous():
-        raise ValueError("latent f must be contiguous")
-    eff_tol = max(float(tol), LAPLACE_MIN_TOL)
-    logz, grad, iters, bad = ext.fused_laplace_evidence(
-        X, y.to(torch.float32), f, scale, float(C), float(nu), eff_tol,
-        min(int(max_newton), 40))
+    logz, grad, iters, bad = _fused_laplace(ext.fused_laplace_evidence, cs,
+                                            theta, X, y, f, tol, max_newton)
     # one device->host transfer for everything
     stats = torch.cat([logz.sum().reshape(1), bad.sum().double().reshape(1),
                        grad.sum(0)]).cpu().numpy()
@@ -207,68 +200,25 @@ _SYNC_TILE_CACHE: dict = {}
 
 
 def _syrk_sync_tiles(m: int, device):
-    """XCD-clustered tile lists for the k-synchronized SYRK.
-
-    One block owns one 256x256 output tile for a whole launch, so a launch
-    carries at most 224 tiles (blocks beyond the resident set would break
-    the k-cohort).  The dispatcher places block b on XCD b%8 (observed,
-    speed-only), so each launch list interleaves 8 per-XCD sequences whose
-    tiles are sorted by 2x4-tile patches — an XCD's resident tiles then
-    share a handful of 256-row/column operand windows that fit its 4 MB L2
-    at the 256-k phase width."""
-    import os
-    pr, pc = (int(v) for v in
-              os.environ.get("SPARK_GP_AMD_SYRK_PATCH", "2x4").split("x"))
-    key = (m, str(device), pr, pc)
-    if key in _SYNC_TILE_CACHE:
-        return _SYNC_TILE_CACHE[key]
-    ntile = (m + 255) // 256
-    tiles = [(ti, tj) for ti in range(ntile) for tj in range(ti + 1)]
-    tiles.sort(key=lambda t: (t[0] // pr, t[1] // pc))
-    launches = []
-    CAP = 224
-    for s in range(0, len(tiles), CAP):
-        grp = tiles[s:s + CAP]
-        per = (len(grp) + 7) // 8
-        L = [(-1, -1)] * (per * 8)
-        for x in range(8):
-            seg = grp[x * per:(x + 1) * per]
-            for j, t in enumerate(seg):
-                L[j * 8 + x] = t
-        tt = torch.tensor(L, dtype=torch.int32, device=device)
-        launches.append((tt, len(grp)))
-    _SYNC_TILE_CACHE[key] = launches
-    return launches
-
-
-def _syrk_dispatch(KcT, KlT, KK, m: int):
-    import os
-    ntile = (m + 255) // 256
-    tiles = ntile * (ntile + 1) // 2
-    # k-synchronized persistent path wins once the tile set exceeds the
-    # resident-block set (measured: m=8192 627 vs 494 TF at kpb=128;
-    # m=4096 the split-k kernel is still ahead, 526 vs ~494 —
-    # PROFILES.md round-2 SYRK section)
-    if tiles > 256 and os.environ.get("SPARK_GP_AMD_SYRK_SYNC", "1") == "1":
-        for tt, nact in _syrk_sync_tiles(m, KK.device):
-            ext.syrk_bf16_sync_acc(KcT, KlT, KK, tt, 128, nact)
-        return
-    # split_k: measured sweep (scripts/bench_syrk.py --sweep, r2) — see
-    # PROFILES.md; shorter per-block k-ranges keep the drifting column
-    # windows closer to L3 residency
-    split_k = max(1, min(16, round(4096 / tiles)))
-    ext.syrk_bf16_acc(KcT, KlT, KK, split_k)
+    """ppa_plan.syrk_sync_tile_lists uploaded once per (m, device, patch)."""
+    patch = ppa_plan.syrk_sync_patch()
+    key = (m, str(device), patch)
+    if key not in _SYNC_TILE_CACHE:
+        _SYNC_TILE_CACHE[key] = [
+            (torch.tensor(tiles, dtype=torch.int32, device=device), nactive)
+            for tiles, nactive in ppa_plan.syrk_sync_tile_lists(m, patch)]
+    return _SYNC_TILE_CACHE[key]
 
 
 def kmn_knm_and_kmny(kernel: Kernel, active: torch.Tensor,
                      X: torch.Tensor, y: torch.Tensor,
-                     chunk_rows: int = 131072, precision: str = "fp64"
+                     chunk_rows: int = 262144, precision: str = "fp64"
                      ) -> Tuple[torch.Tensor, torch.Tensor]:
     cs = compile_kernel(kernel)
     theta = kernel.get_hyperparameters()
     n, d = X.shape
     m = active.shape[0]
-    C = cs.amp(theta)
+    C = float(cs.amp(theta))
     s2 = _s2_vector(cs, theta, d, X.device)
     act32 = active.to(torch.float32).contiguous()
     y32 = y.to(torch.float32)
@@ -281,7 +231,7 @@ def kmn_knm_and_kmny(kernel: Kernel, active: torch.Tensor,
         for s in range(0, n, chunk_rows):
             e = min(n, s + chunk_rows)
             Kc = ext.cross_kernel_tile(X[s:e].contiguous(), act32, s2,
-                                       float(C), False, False)[0]
+                                       C, False, False)[0]
             K64 = Kc.double()
             KK64 += K64.transpose(0, 1) @ K64
             Ky += K64.transpose(0, 1) @ y[s:e].double()
@@ -289,45 +239,40 @@ def kmn_knm_and_kmny(kernel: Kernel, active: torch.Tensor,
 
     # 'mixed': hi/lo bf16 split — KK += hi^T hi + hi^T lo + lo^T hi on the
     # MFMA SYRK keeps input-quantization error at fp32 class while running
-    # at bf16 matrix-core rate
+    # at bf16 matrix-core rate.  ppa_plan picks the K_nm generator, the SYRK
+    # kernel, split_k and the chunk length.
+    plan = ppa_plan.ppa_plan(m, d, X.dtype, chunk_rows)
     KK = torch.zeros(m, m, dtype=torch.float32, device=X.device)
-    # MFMA cross tile (K1 plan): sqdist via ||x'||^2 + ||a'||^2 - 2 x'.a'
-    # on f32 matrix cores with pre-scaled coordinates, writing ONLY the
-    # transposed hi/lo copies the SYRK stages from and accumulating
-    # Ky += K^T y in the same launch.  The elementwise kernel (~3 VALU
-    # issues per (element, dim)) remains as the fallback/AB path.
-    #
-    # Fused path (default where the gate allows): the SYRK blocks generate
-    # their K_nm operand windows themselves from the same pre-scaled inputs
-    # and formula, so no [m, chunk] hi/lo buffers are written or re-read
-    # (SPARK_GP_AMD_PPA_FUSED=0 selects the two-kernel path for A/B).
-    import os
-    use_mfma = os.environ.get("SPARK_GP_AMD_CROSS_MFMA", "1") == "1"
-    use_fused = (use_mfma and ppa_fused_gate(m, d, X.dtype)
-                 and bool(ext.ppa_fused_supported(m, d)))
-    if use_mfma:
+    if plan.generator != "elementwise":
+        # pre-scaled coordinates and their squared norms: the generators
+        # compute sqdist as ||x'||^2 + ||a'||^2 - 2 x'.a'
         svec = _scale_vector(cs, theta, d, X.device)
         As = (act32 * svec).contiguous()
         na = (As * As).sum(-1).contiguous()
-    if use_fused:
-        chunk_rows = ppa_fused_chunk_rows(chunk_rows)
-    for s in range(0, n, chunk_rows):
-        e = min(n, s + chunk_rows)
-        if use_mfma:
+    if plan.syrk == "sync":
+        sync_tiles = _syrk_sync_tiles(m, X.device)
+    for s in range(0, n, plan.chunk_rows):
+        e = min(n, s + plan.chunk_rows)
+        yc = y32[s:e].contiguous()
+        if plan.generator != "elementwise":
+            # assigned here, not in a helper: the previous chunk's Xs is
+            # released before the Xs * Xs temporary is allocated
             Xs = (X[s:e] * svec).contiguous()
             nx = (Xs * Xs).sum(-1).contiguous()
-            if use_fused:
-                ext.ppa_fused_acc(Xs, As, nx, na, float(C),
-                                  y32[s:e].contiguous(), Ky, KK,
-                                  ppa_fused_split_k(m))
-                continue
-            KcT, KlT = ext.cross_mfma_ppa(Xs, As, nx, na, float(C),
-                                          y32[s:e].contiguous(), Ky)
+        if plan.generator == "fused":
+            ext.ppa_fused_acc(Xs, As, nx, na, C, yc, Ky, KK, plan.split_k)
+            continue
+        if plan.generator == "mfma":
+            KcT, KlT = ext.cross_mfma_ppa(Xs, As, nx, na, C, yc, Ky)
         else:
             KcT, KlT = ext.cross_kernel_tile_ppa(X[s:e].contiguous(), act32,
-                                                 s2, float(C),
-                                                 y32[s:e].contiguous(), Ky)
-        _syrk_dispatch(KcT, KlT, KK, m)
+                                                 s2, C, yc, Ky)
+        if plan.syrk == "sync":
+            for tiles, nactive in sync_tiles:
+                ext.syrk_bf16_sync_acc(KcT, KlT, KK, tiles,
+                                       ppa_plan.SYNC_KPB, nactive)
+        else:
+            ext.syrk_bf16_acc(KcT, KlT, KK, plan.split_k)
     return KK.double(), Ky
 
 
@@ -361,24 +306,15 @@ def _dpotrf(Apad: torch.Tensor):
 
 
 def chol_factor64(M: torch.Tensor, max_tries: int = 6):
-    """Blocked fp64 Cholesky with the escalating-jitter ladder of
-    ppa._chol_with_jitter (PD check = the factor's breakdown flag, not an
+    """Blocked fp64 Cholesky over the escalating-jitter ladder of
+    ppa.jitter_ladder (PD check = the factor's breakdown flag, not an
     eigSym pass).  Returns (L_padded [mp,mp], diag-block inverses V)."""
-    from ..ppa import NotPositiveDefiniteError
-    Apad = _pad64_spd(M)
-    V, bad = _dpotrf(Apad)
-    if int(bad.item()) == 0:
-        return Apad, V
-    scale = float(M.diagonal().abs().mean())
-    eps = 1e-12
-    m = M.shape[0]
-    for _ in range(max_tries):
-        jit = eps * scale * torch.eye(m, dtype=M.dtype, device=M.device)
-        Apad = _pad64_spd(M + jit)
+    from ..ppa import NotPositiveDefiniteError, jitter_ladder
+    for Mj in jitter_ladder(M, max_tries):
+        Apad = _pad64_spd(Mj)
         V, bad = _dpotrf(Apad)
         if int(bad.item()) == 0:
             return Apad, V
-        eps *= 100.0
     raise NotPositiveDefiniteError()
 
 

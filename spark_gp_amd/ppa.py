@@ -54,10 +54,9 @@ def magic_vector_matrix(kernel: Kernel, KK: torch.Tensor, Ky: torch.Tensor,
     On GPU the factorization/solves/inverses run on the hand-written K13
     kernels (big_chol.hip: blocked fp64 Cholesky + MFMA-f64 GEMM tiles);
     the torch path below is the CPU oracle."""
-    if KK.is_cuda and not ops._force_torch():
-        hip = ops._load_hip()
-        if ops._require_hip_or_fallback("magic_vector_matrix"):
-            return hip.magic_vector_matrix(kernel, KK, Ky, active)
+    res = ops.magic_vector_matrix(kernel, KK, Ky, active)
+    if res is not None:
+        return res
     active64 = active.double()
     Kmm = kernel.training_kernel(active64)            # includes noise diag
     nu = kernel.white_noise_var()
@@ -71,25 +70,29 @@ def magic_vector_matrix(kernel: Kernel, KK: torch.Tensor, Ky: torch.Tensor,
     return magic_vector, magic_matrix
 
 
-def _chol_with_jitter(M: torch.Tensor, max_tries: int = 6) -> torch.Tensor:
-    """Cholesky with an escalating-jitter ladder.
+def jitter_ladder(M: torch.Tensor, max_tries: int = 6):
+    """Yields M, then M + eps_rel * mean|diag(M)| * I for ``max_tries``
+    rungs eps_rel = 1e-12, 1e-10, ... (1e-2 at the default six).
 
     The reference asserts PD via eigSym and throws immediately
     (``ProjectedGaussianProcessHelper.scala:62-65``).  Here, matrices that are
     PD in exact arithmetic can be numerically indefinite (fp32/bf16
-    accumulation of K_mn K_nm on the GPU path), so failures retry with
-    jitter = eps_rel * mean(diag) escalating 1e-12 .. 1e-2 before raising —
-    a strict robustness superset of the reference behavior."""
-    L, info = torch.linalg.cholesky_ex(M)
-    if int(info) == 0:
-        return L
+    accumulation of K_mn K_nm on the GPU path), so a failed factorization
+    retries on the next rung before raising — a strict robustness superset
+    of the reference behavior."""
+    yield M
     scale = float(M.diagonal().abs().mean())
     eps = 1e-12
     for _ in range(max_tries):
-        jit = eps * scale * torch.eye(M.shape[-1], dtype=M.dtype,
-                                      device=M.device)
-        L, info = torch.linalg.cholesky_ex(M + jit)
+        yield M + eps * scale * torch.eye(M.shape[-1], dtype=M.dtype,
+                                          device=M.device)
+        eps *= 100.0
+
+
+def _chol_with_jitter(M: torch.Tensor, max_tries: int = 6) -> torch.Tensor:
+    """Cholesky over the escalating-jitter ladder."""
+    for Mj in jitter_ladder(M, max_tries):
+        L, info = torch.linalg.cholesky_ex(Mj)
         if int(info) == 0:
             return L
-        eps *= 100.0
     raise NotPositiveDefiniteError()
