@@ -137,6 +137,18 @@ bool fused_expert_nll_supported(int64_t k, int64_t d) {
   return nll_lds_bytes((int)k, (int)d) <= GEOM_LDS_MAX;
 }
 
+// Workgroups of fused_expert_nll_kernel the HIP runtime reports resident per
+// CU (hipOccupancyMaxActiveBlocksPerMultiprocessor) at the launch's real
+// block size and dynamic LDS, on the current device.
+int64_t fused_expert_nll_occupancy(int64_t k, int64_t d) {
+  TORCH_CHECK(k >= 1 && k <= 128, "k must be in [1, 128], got ", k);
+  TORCH_CHECK(d >= 1 && d <= 128, "d must be in [1, 128], got ", d);
+  int wgs = 0;
+  check_hip(fused_expert_nll_resident_wgs((int)k, (int)d, &wgs),
+            "fused_expert_nll_occupancy");
+  return wgs;
+}
+
 // The elementwise RBF/ARD tile in both of its uses.  want_cm: write the
 // [c, m] copies (hi, and lo with hilo); want_t: write the transposed hi/lo
 // pair; y/Ky (both or neither): also accumulate Ky += K^T y from the fp32
@@ -537,6 +549,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("fused_expert_nll_profile", &fused_expert_nll_impl,
           "same, with per-phase wall_clock64 boundaries appended");
   mod.def("fused_expert_nll_supported", &fused_expert_nll_supported);
+  mod.def("fused_expert_nll_occupancy", &fused_expert_nll_occupancy,
+          "resident workgroups per CU of the expert kernel at (k, d)");
   mod.def("cross_mfma_ppa", &cross_mfma_ppa,
           "MFMA sqdist cross tile + fused K^T y (K1 plan, CDNA4)");
   mod.def("ppa_fused_acc", &ppa_fused_acc,

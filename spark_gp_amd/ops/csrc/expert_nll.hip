@@ -16,7 +16,7 @@
 //   C  blocked right-looking Cholesky, IN PLACE, with look-ahead: per
 //      8-column sub-block q of each 32-column block, wave 0 factors AND
 //      inverts the 8x8 sub-diagonal (row-per-lane on 8 lanes, cross-lane
-//      traffic via __shfl at STATIC register indices; branchless
+//      traffic via v_readlane broadcasts from STATIC lanes; branchless
 //      frexp-accumulated log-det) WHILE waves 1-7 apply chunk q of the
 //      previous panel's rank-32 trailing update; then ALL 512 threads do
 //      the intra-block panel/trailing and, after the 4 sub-blocks, the
@@ -39,8 +39,11 @@
 // Inner products with a contiguous operand are float4 (ds_read_b128)
 // vectorized over 16-B-aligned LDS rows (strides padded to multiples of 4
 // floats); the rest are multi-accumulator-unrolled scalars.  Single
-// k x SA working buffer + one k x 36 temp => ~69 KB LDS at k=100, two
-// experts resident per CU.
+// k x SA working buffer + one (k-32) x 36 temp; the scaled features are
+// not kept in LDS (B and H take their fragments from global X) => 52 KB
+// LDS at k=100, and 80 VGPRs at 6 waves/SIMD: three experts resident per
+// CU (profiles/PROFILES.md round 4; fused_expert_nll_resident_wgs asks
+// the runtime).
 //
 // Numerics: fp32 storage/factorization, fp64 scalar accumulation.  Experts
 // whose fp32 Cholesky breaks down are flagged in out_bad and recomputed on
@@ -62,13 +65,13 @@ typedef __attribute__((ext_vector_type(4))) float mfma_f32x4;
 struct NllLds {
   float* A;     // k * SA (SA = k+1 up-aligned to 4): lower K -> L/V ->
                 // K^-1 -> W0; upper: Kb cache
-  float* T;     // temp: max(k*36, 32*SA, 448)
-  float* X;     // k * dp4 SCALED features x' = x o s (16-B-aligned rows)
+  float* T;     // temp: nll_tsz(k, d)
   float* yb;    // k
   float* alpha; // k
   float* tvec;  // k
   float* rrow;  // k
-  float* s2;    // d
+  float* s2;    // d: scale^2
+  float* sc;    // d: scale (x' = x o scale is formed in registers)
   double* red;  // 8 (per-wave partials)
   double* misc; // 2: logdet, scratch
   int* bad;     // 1
@@ -81,18 +84,41 @@ __device__ inline NllLds carve(char* base, int k, int d) {
   L.red = (double*)p;   L.misc = L.red + 8;
   p += a16(sizeof(double) * 10);
   L.A = (float*)p;      p += a16(sizeof(float) * (size_t)k * geom_sa(k));
-  L.T = (float*)p;      p += a16(sizeof(float) * geom_tsz(k));
-  L.X = (float*)p;      p += a16(sizeof(float) * (size_t)k * geom_dp4(d));
+  L.T = (float*)p;      p += a16(sizeof(float) * nll_tsz(k, d));
   L.yb = (float*)p;     p += a16(sizeof(float) * k);
   L.alpha = (float*)p;  p += a16(sizeof(float) * k);
   L.tvec = (float*)p;   p += a16(sizeof(float) * k);
   L.rrow = (float*)p;   p += a16(sizeof(float) * k);
   L.s2 = (float*)p;     p += a16(sizeof(float) * d);
+  L.sc = (float*)p;     p += a16(sizeof(float) * d);
   L.bad = (int*)p;
   return L;
 }
 
-extern "C" __global__ void __launch_bounds__(WG, 4)
+// ||x o s||^2 of one global row, in the order dotv(x', x', 0, d) sums it
+// (four strided partials, pairwise fold, scalar tail).
+__device__ inline float scaled_sqnorm(const float* __restrict__ x,
+                                      const float* sc, int d) {
+  float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
+  int c = 0;
+  for (; c + 3 < d; c += 4) {
+    const float v0 = x[c] * sc[c], v1 = x[c + 1] * sc[c + 1];
+    const float v2 = x[c + 2] * sc[c + 2], v3 = x[c + 3] * sc[c + 3];
+    a0 += v0 * v0; a1 += v1 * v1; a2 += v2 * v2; a3 += v3 * v3;
+  }
+  float s = (a0 + a1) + (a2 + a3);
+  for (; c < d; ++c) {
+    const float v = x[c] * sc[c];
+    s += v * v;
+  }
+  return s;
+}
+
+// MFMA k-steps whose global X fragments are fetched together, so that a
+// tile pays one memory latency per XCH*4 contraction indices
+#define XCH 4
+
+extern "C" __global__ void __launch_bounds__(WG, 6)
 fused_expert_nll_kernel(const float* __restrict__ Xg,
                         const float* __restrict__ yg,
                         const float* __restrict__ scale,   // [d]
@@ -111,26 +137,23 @@ fused_expert_nll_kernel(const float* __restrict__ Xg,
   PH(0);
   NllLds S = carve(lds_raw, k, d);
   const int SA = (int)geom_sa(k);
-  const int dp = (int)geom_dp4(d);
   const int e = blockIdx.x;
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
+  int tid = threadIdx.x;
+  int lane = tid & 63;
   const int nblk = (k + NB - 1) / NB;
   const float* Xe = Xg + (size_t)e * k * d;
   const float* ye = yg + (size_t)e * k;
 
-  // ---- A: stage SCALED X' = X o s, y, s2 ----------------------------
-  // Scaled coordinates make the kernel build a plain GEMM
+  // ---- A: stage y, scale, s2 ---------------------------------------
+  // Scaled coordinates x' = x o s make the kernel build a plain GEMM
   // (q = ||x'||^2 + ||a'||^2 - 2 x'.a') and the gradient contraction
-  // runs in scaled space, de-scaled by s2 at output (H phase).
+  // runs in scaled space, de-scaled by s2 at output (H phase).  x' is
+  // not staged: phases B and H form their fragments from global X (12.8
+  // KB per expert at k=100, d=32, cache-resident) times S.sc.
   for (int j = tid; j < d; j += WG) {
     float s = scale[j];
+    S.sc[j] = s;
     S.s2[j] = s * s;
-  }
-  __syncthreads();
-  for (int i = tid; i < k * d; i += WG) {
-    int a = i / d, j = i - a * d;
-    S.X[a * dp + j] = Xe[i] * scale[j];
   }
   for (int i = tid; i < k; i += WG) S.yb[i] = ye[i];
   if (tid == 0) { *S.bad = 0; S.misc[0] = 0.0; }
@@ -144,7 +167,7 @@ PH(1);
   // through S.alpha (free until phase E).
   {
     for (int a = tid; a < k; a += WG)
-      S.alpha[a] = dotv(S.X + (size_t)a * dp, S.X + (size_t)a * dp, 0, d);
+      S.alpha[a] = scaled_sqnorm(Xe + (size_t)a * d, S.sc, d);
     __syncthreads();
     const int nt = (k + 15) / 16;
     const int ntri = nt * (nt + 1) / 2;
@@ -156,13 +179,20 @@ PH(1);
       mfma_f32x4 acc = {0.f, 0.f, 0.f, 0.f};
       const int ia = ti * 16 + l16;        // A-fragment row
       const int jb = tj * 16 + l16;        // B-fragment column
-      for (int k0 = 0; k0 < d; k0 += 4) {
-        const int fk = k0 + kg;
-        const float av = (ia < k && fk < d) ? S.X[(size_t)ia * dp + fk]
-                                            : 0.f;
-        const float bv = (jb < k && fk < d) ? S.X[(size_t)jb * dp + fk]
-                                            : 0.f;
-        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bv, acc, 0, 0, 0);
+      for (int k0 = 0; k0 < d; k0 += 4 * XCH) {
+        float av[XCH], bv[XCH];
+#pragma unroll
+        for (int u = 0; u < XCH; ++u) {
+          const int fk = k0 + 4 * u + kg;
+          const float s = fk < d ? S.sc[fk] : 0.f;
+          av[u] = (ia < k && fk < d) ? Xe[(size_t)ia * d + fk] * s : 0.f;
+          bv[u] = (jb < k && fk < d) ? Xe[(size_t)jb * d + fk] * s : 0.f;
+        }
+#pragma unroll
+        for (int u = 0; u < XCH; ++u)
+          if (k0 + 4 * u < d)
+            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av[u], bv[u], acc,
+                                                       0, 0, 0);
       }
       // D map: row = (lane>>4)*4 + r, col = lane&15
 #pragma unroll
@@ -183,7 +213,7 @@ PH(2);
   // ---- C/D: in-place blocked Cholesky + triangular inverse ---------
   // (shared machinery: linalg_lds.h)  A: lower K -> V = L^-1; upper Kb
   // cache untouched; log|K| into misc[0]; bad flag on fp32 breakdown.
-  chol_invert_lower(S.A, S.T, k, SA, tid, lane, S.bad, S.misc,
+  chol_invert_lower(S.A, S.T, k, SA, tid, S.bad, S.misc,
                     out_clk ? out_clk + (size_t)e * 20 + 12 : nullptr);
   if (*S.bad) {
     if (tid == 0) {
@@ -195,6 +225,10 @@ PH(2);
   }
   // log|K| = 2 sum log L_ii = sum log(ajj before sqrt), accumulated in C1
   const double logdet = S.misc[0];
+  // as in chol_invert_lower: phases E..H recompute their thread indices
+  // instead of keeping phase B's alive across the factorization
+  asm volatile("" : "+v"(tid));
+  lane = tid & 63;
 
 PH(3);
   PH(4);
@@ -321,13 +355,22 @@ PH(8);
       mfma_f32x4 a = {0.f, 0.f, 0.f, 0.f};
       const int fi = ti * 16 + l16;         // W0 row (A fragment)
       const int fj = tj * 16 + l16;         // X' column (B fragment)
-      for (int c0 = 0; c0 < k; c0 += 4) {
-        const int cc = c0 + kg;
-        const float av = (fi < k && cc < k)
-                             ? S.A[(size_t)fi * SA + cc] : 0.f;
-        const float bv = (cc < k && fj < d)
-                             ? S.X[(size_t)cc * dp + fj] : 0.f;
-        a = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bv, a, 0, 0, 0);
+      const float sj = fj < d ? S.sc[fj] : 0.f;
+      for (int c0 = 0; c0 < k; c0 += 4 * XCH) {
+        float bv[XCH];
+#pragma unroll
+        for (int u = 0; u < XCH; ++u) {
+          const int cc = c0 + 4 * u + kg;
+          bv[u] = (cc < k && fj < d) ? Xe[(size_t)cc * d + fj] * sj : 0.f;
+        }
+#pragma unroll
+        for (int u = 0; u < XCH; ++u) {
+          const int cc = c0 + 4 * u + kg;
+          if (c0 + 4 * u >= k) break;
+          const float av = (fi < k && cc < k)
+                               ? S.A[(size_t)fi * SA + cc] : 0.f;
+          a = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bv[u], a, 0, 0, 0);
+        }
       }
       // fold: per fragment element (row gi, col gj):
       //   part += 2 x'(gi,gj) * (x'(gi,gj) * r_gi - wx)
@@ -337,8 +380,13 @@ PH(8);
       for (int r = 0; r < 4; ++r) {
         const int gi = ti * 16 + kg * 4 + r;
         if (gi < k && gj < d) {
-          const float x = S.X[(size_t)gi * dp + gj];
-          part += 2.0f * x * (x * S.rrow[gi] - a[r]);
+          // spelled out so that it does not depend on what the compiler
+          // chooses to contract: rounded product, rounded difference,
+          // fused accumulate
+#pragma clang fp contract(off)
+          const float x = Xe[(size_t)gi * d + gj] * sj;
+          const float xr = x * S.rrow[gi];
+          part = __builtin_fmaf(2.0f * x, xr - a[r], part);
         }
       }
       // reduce the 4 row-groups sharing this column: lanes l, l+16,
@@ -369,22 +417,37 @@ PH(8);
   }
 }
 
+// dynamic LDS of a launch; 0 when the shape is not supported
+static size_t nll_launch_lds(int k, int d) {
+  if (k < 1 || k > 128 || d > 128) return 0;
+  size_t lds = nll_lds_bytes(k, d);
+  // occupancy experiment knob: lower the resident WGs per CU by padding
+  // the LDS ask (measures how much co-resident expert WGs overlap)
+  if (const char* pad = getenv("SPARK_GP_AMD_NLL_LDS_PAD"))
+    lds += (size_t)atol(pad);
+  return lds <= GEOM_LDS_MAX ? lds : 0;
+}
+
 // host-callable launcher (used by bindings.cpp)
 extern "C" hipError_t launch_fused_expert_nll(
     const float* X, const float* y, const float* scale,
     float amp, float noise, int E, int k, int d,
     double* out_nll, double* out_sumW0, double* out_trG, double* out_contr,
     int* out_bad, unsigned long long* out_clk, hipStream_t stream) {
-  size_t lds = nll_lds_bytes(k, d);
-  // occupancy experiment knob: force 1 WG/CU by padding the LDS ask
-  // (measures how much the usual 2 co-resident expert WGs overlap)
-  if (const char* pad = getenv("SPARK_GP_AMD_NLL_LDS_PAD"))
-    lds += (size_t)atol(pad);
-  if (lds > GEOM_LDS_MAX || k > 128 || d > 128)
-    return hipErrorInvalidConfiguration;
+  const size_t lds = nll_launch_lds(k, d);
+  if (!lds) return hipErrorInvalidConfiguration;
   hipLaunchKernelGGL(fused_expert_nll_kernel, dim3(E), dim3(WG), lds, stream,
                      X, y, scale, amp, noise, k, d,
                      out_nll, out_sumW0, out_trG, out_contr, out_bad,
                      out_clk);
   return hipGetLastError();
+}
+
+// workgroups of the kernel the runtime keeps resident per CU at the block
+// size and dynamic LDS launch_fused_expert_nll uses for (k, d)
+extern "C" hipError_t fused_expert_nll_resident_wgs(int k, int d, int* out) {
+  const size_t lds = nll_launch_lds(k, d);
+  if (!lds) return hipErrorInvalidConfiguration;
+  return hipOccupancyMaxActiveBlocksPerMultiprocessor(
+      out, fused_expert_nll_kernel, WG, lds);
 }

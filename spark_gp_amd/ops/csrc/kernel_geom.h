@@ -38,15 +38,29 @@ static GEOM_HD inline size_t geom_dp4(int d) {
   return (size_t)((d + 4) & ~3);
 }
 
-// LDS bytes of fused_expert_nll_kernel; region order is NllLds's carve
+// temp buffer of fused_expert_nll_kernel, in floats: only the terms its own
+// phases use (geom_tsz's 32*SA term is laplace.hip's).  Vq/TS of the 8x8
+// factor: 448; the C2 panel copy and D's U: (k-32) rows of stride 36; H's
+// per-row-tile partials: ceil(k/16)*d.
+static GEOM_HD inline size_t nll_tsz(int k, int d) {
+  size_t t = 448;
+  if (k > 32 && t < (size_t)(k - 32) * 36) t = (size_t)(k - 32) * 36;
+  const size_t h = (size_t)((k + 15) / 16) * (size_t)d;
+  if (t < h) t = h;
+  return t;
+}
+
+// LDS bytes of fused_expert_nll_kernel; region order is NllLds's carve.
+// The scaled features are not kept in LDS (phases B and H read their MFMA
+// fragments from global X), which is what lets three experts share a CU
+// at k = 100: 53 344 B against floor(160 KiB / 3) = 54 613 B.
 static GEOM_HD inline size_t nll_lds_bytes(int k, int d) {
   size_t off = 0;
   off += a16(sizeof(double) * 10);                      // red + misc
   off += a16(sizeof(float) * (size_t)k * geom_sa(k));   // A
-  off += a16(sizeof(float) * geom_tsz(k));              // T
-  off += a16(sizeof(float) * (size_t)k * geom_dp4(d));  // X
+  off += a16(sizeof(float) * nll_tsz(k, d));            // T
   off += 4 * a16(sizeof(float) * k);                    // yb alpha tvec rrow
-  off += a16(sizeof(float) * d);                        // s2
+  off += 2 * a16(sizeof(float) * d);                    // s2 sc
   off += 16;                                            // bad (+pad)
   return off;
 }

@@ -233,7 +233,7 @@ fused_laplace_kernel(const float* __restrict__ Xg,   // [E, k, d]
       }
     }
     __syncthreads();
-    chol_invert_lower(S.A, S.T, k, SA, tid, lane, S.bad, S.misc);
+    chol_invert_lower(S.A, S.T, k, SA, tid, S.bad, S.misc);
     if (*S.bad) break;
     // z = V u (lower); t2 = V^T z
     for (int i = tid; i < k; i += WG)
@@ -303,7 +303,7 @@ fused_laplace_kernel(const float* __restrict__ Xg,   // [E, k, d]
       }
     }
     __syncthreads();
-    chol_invert_lower(S.A, S.T, k, SA, tid, lane, S.bad, S.misc);
+    chol_invert_lower(S.A, S.T, k, SA, tid, S.bad, S.misc);
   }
   if (EV && !*S.bad) {
     // a = b - sqw V^T V (sqw (K b));  fc = K a;  psi;  logZ

@@ -18,6 +18,8 @@ hipError_t launch_fused_expert_nll(
     double* out_trG, double* out_contr, int* out_bad,
     unsigned long long* out_clk, hipStream_t stream);
 
+hipError_t fused_expert_nll_resident_wgs(int k, int d, int* out);
+
 // ---- laplace.hip ----------------------------------------------------------
 hipError_t launch_fused_laplace_newton(
     const float* X, const float* y, float* f, const float* scale, float amp,

@@ -35,6 +35,15 @@ __device__ inline double block_sum(double v, double* red, int tid) {
   return out;
 }
 
+// Broadcast of lane `src`'s x to the whole wave, `src` a compile-time
+// constant: v_readlane_b32 into an SGPR.  Bitwise what __shfl(x, src, 64)
+// returns, without the ds_bpermute round trip through the LDS pipe that
+// the other resident waves keep busy.  The wave must be converged.
+__device__ inline float bcast_lane(float x, int src) {
+  return __builtin_bit_cast(
+      float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, x), src));
+}
+
 // flat f -> (a, b) with a >= b in a lower triangle (incl. diagonal)
 __device__ inline void tri_decode(int f, int& a, int& b) {
   a = (int)((sqrtf(8.f * (float)f + 1.f) - 1.f) * 0.5f);
@@ -102,17 +111,22 @@ __device__ inline float dot4(const float* p, int sp, const float* q, int sq,
 // In place on the lower triangle of Abuf (k x k, row stride SA):
 // K -> L -> V = L^{-1} (lower).  Strict upper of Abuf is never touched.
 // log|K| accumulates into misc[0]; *bad set to 1 (indefinite) or 2
-// (non-finite pivot) on breakdown.  Tbuf: >= max(k*36, 448) floats
+// (non-finite pivot) on breakdown.  Tbuf: >= max((k-32)*36, 448) floats
 // scratch, 16-B aligned; SA must be a multiple of 4 (vectorized dots).
 // All WG threads must call (contains __syncthreads).
 __device__ inline void chol_invert_lower(float* Abuf, float* Tbuf,
                                          const int k, const int SA,
-                                         const int tid, const int lane,
-                                         int* bad, double* misc,
+                                         const int tid_in, int* bad,
+                                         double* misc,
                                          unsigned long long* jclk = nullptr) {
   // jclk (profiling only): accumulated cycles into
   //   [0] phase1  [1] phase2 wall  [2] wave0 span  [3] waves1-7 span
   //   [4] C2 panel solve  [5] D off-diag trtri
+  // tid passes through an empty asm at the top of every block-column
+  // iteration: values derived from it are then recomputed per iteration
+  // (a few VALU ops) instead of being hoisted and kept live across the
+  // whole factorization, which at 6 waves/SIMD meant scratch spills.
+  int tid = tid_in;
   const int nblk = (k + NB - 1) / NB;
     // ---- C: blocked in-place Cholesky with look-ahead ----------------
   // Right-looking, restructured so the serial diagonal factorization
@@ -122,6 +136,8 @@ __device__ inline void chol_invert_lower(float* Abuf, float* Tbuf,
   //           J-1's update to the remaining trailing columns
   //   phase3: panel solve for block J (copy + GEMM vs inverted diagonal)
   for (int J = 0; J < nblk; ++J) {
+    asm volatile("" : "+v"(tid));
+    const int lane = tid & 63;
     const int jb = J * NB;
     const int bs = min(NB, k - jb);
     float* D = Abuf + (size_t)jb * SA + jb;   // diag block, stride SA
@@ -170,7 +186,8 @@ __device__ inline void chol_invert_lower(float* Abuf, float* Tbuf,
         __builtin_amdgcn_s_setprio(1);
         {
           // 8x8 factor + trtri on lanes 0..7, ROW j per lane, cross-lane
-          // traffic via __shfl (ds_bpermute).  Row-per-lane keeps every
+          // traffic via bcast_lane (every source lane is a compile-time
+          // constant, so no LDS-pipe round trip).  Row-per-lane keeps every
           // runtime-varying access at a STATIC register index: the rank-1
           // scalar is the lane's own row[ss], and the update bounds
           // c in (ss, 7] are compile-time — the earlier column-per-lane
@@ -197,7 +214,7 @@ __device__ inline void chol_invert_lower(float* Abuf, float* Tbuf,
           for (int ss = 0; ss < 8; ++ss) {
             float l[8];                 // column ss: l[c] = lane c's row[ss]
 #pragma unroll
-            for (int c = 0; c < 8; ++c) l[c] = __shfl(row[ss], c, 64);
+            for (int c = 0; c < 8; ++c) l[c] = bcast_lane(row[ss], c);
             const float piv = l[ss];
             if (ss < sbs) {
               const bool fin = isfinite(piv);
@@ -220,7 +237,7 @@ __device__ inline void chol_invert_lower(float* Abuf, float* Tbuf,
           // rs vector from the diagonal lanes (rs_c = lane c's myrs)
 #pragma unroll
           for (int c = 0; c < 8; ++c) {
-            rsv = __shfl(myrs, c, 64);
+            rsv = bcast_lane(myrs, c);
             row[c] *= rsv;
           }
           if (lane < 8 && j < sbs) {    // write L back (row j)
@@ -237,7 +254,7 @@ __device__ inline void chol_invert_lower(float* Abuf, float* Tbuf,
           for (int i = 0; i < 8; ++i) {
             float rowi[8];
 #pragma unroll
-            for (int c = 0; c < 8; ++c) rowi[c] = __shfl(row[c], i, 64);
+            for (int c = 0; c < 8; ++c) rowi[c] = bcast_lane(row[c], i);
             if (j < i) {
               float sacc = 0.f;
 #pragma unroll
@@ -429,6 +446,8 @@ __device__ inline void chol_invert_lower(float* Abuf, float* Tbuf,
   // already-inverted trailing V (c <= row) and the second GEMM masks
   // B-fragments to V_JJ's lower triangle (t >= j).
   for (int J = nblk - 2; J >= 0; --J) {
+    asm volatile("" : "+v"(tid));
+    const int lane = tid & 63;
     const int jb = J * NB;
     const int bs = NB;                       // J < nblk-1 => full block
     const int t0 = jb + bs;
