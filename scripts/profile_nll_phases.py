@@ -42,6 +42,10 @@ total = mean.sum()
 print(f"sum of phases: {total:.2f} us (mean per expert)")
 for i in range(9):
     print(f"  {phases[i]:>8}: {mean[i]:8.2f} us  ({100*mean[i]/total:4.1f}%)")
+# slot 10: end of phase B's first staging pass (0 on the global-fragment path)
+if clk[:, 10].max() > 0:
+    print(f"  B, of which staging the first slab: "
+          f"{((clk[:, 10] - clk[:, 1]) / FREQ * 1e6).mean():8.2f} us")
 sub = clk[:, 12:18].mean(0) / FREQ * 1e6
 subnames = ["phase1 diag-pre", "phase2 wall", "wave0 span",
             "waves1-7 span", "C2 panel solve", "D off-diag trtri"]

@@ -39,11 +39,13 @@
 // Inner products with a contiguous operand are float4 (ds_read_b128)
 // vectorized over 16-B-aligned LDS rows (strides padded to multiples of 4
 // floats); the rest are multi-accumulator-unrolled scalars.  Single
-// k x SA working buffer + one (k-32) x 36 temp; the scaled features are
-// not kept in LDS (B and H take their fragments from global X) => 52 KB
-// LDS at k=100, and 80 VGPRs at 6 waves/SIMD: three experts resident per
-// CU (profiles/PROFILES.md round 4; fused_expert_nll_resident_wgs asks
-// the runtime).
+// k x SA working buffer + one (k-32) x 36 temp; the scaled features have
+// no LDS region of their own (B stages them inside the working buffer
+// before anything else is written there and holds its tiles in registers
+// across the barrier in front of its epilogue; H takes its fragments from
+// global X) => 52 KB LDS at k=100, and at most 80 VGPRs at 6 waves/SIMD:
+// three experts resident per CU (profiles/PROFILES.md rounds 4 and 5;
+// fused_expert_nll_resident_wgs asks the runtime).
 //
 // Numerics: fp32 storage/factorization, fp64 scalar accumulation.  Experts
 // whose fp32 Cholesky breaks down are flagged in out_bad and recomputed on
@@ -71,7 +73,7 @@ struct NllLds {
   float* tvec;  // k
   float* rrow;  // k
   float* s2;    // d: scale^2
-  float* sc;    // d: scale (x' = x o scale is formed in registers)
+  float* sc;    // d: scale (x' = x o scale is formed on the fly)
   double* red;  // 8 (per-wave partials)
   double* misc; // 2: logdet, scratch
   int* bad;     // 1
@@ -101,15 +103,20 @@ __device__ inline float scaled_sqnorm(const float* __restrict__ x,
                                       const float* sc, int d) {
   float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
   int c = 0;
+  // spelled out as the compiler has always built it (and as phase B's
+  // staged form repeats it): rounded squares added to the partials, a
+  // fused accumulate in the tail
   for (; c + 3 < d; c += 4) {
+#pragma clang fp contract(off)
     const float v0 = x[c] * sc[c], v1 = x[c + 1] * sc[c + 1];
     const float v2 = x[c + 2] * sc[c + 2], v3 = x[c + 3] * sc[c + 3];
-    a0 += v0 * v0; a1 += v1 * v1; a2 += v2 * v2; a3 += v3 * v3;
+    const float q0 = v0 * v0, q1 = v1 * v1, q2 = v2 * v2, q3 = v3 * v3;
+    a0 = a0 + q0; a1 = a1 + q1; a2 = a2 + q2; a3 = a3 + q3;
   }
   float s = (a0 + a1) + (a2 + a3);
   for (; c < d; ++c) {
     const float v = x[c] * sc[c];
-    s += v * v;
+    s = __builtin_fmaf(v, v, s);
   }
   return s;
 }
@@ -148,8 +155,9 @@ fused_expert_nll_kernel(const float* __restrict__ Xg,
   // Scaled coordinates x' = x o s make the kernel build a plain GEMM
   // (q = ||x'||^2 + ||a'||^2 - 2 x'.a') and the gradient contraction
   // runs in scaled space, de-scaled by s2 at output (H phase).  x' is
-  // not staged: phases B and H form their fragments from global X (12.8
-  // KB per expert at k=100, d=32, cache-resident) times S.sc.
+  // not staged here: phase B stages it inside S.A for its own use, phase
+  // H forms its fragments from global X (12.8 KB per expert at k=100,
+  // d=32, cache-resident) times S.sc.
   for (int j = tid; j < d; j += WG) {
     float s = scale[j];
     S.sc[j] = s;
@@ -165,7 +173,104 @@ PH(1);
   // tiles on v_mfma_f32_16x16x4_f32 (exact fp32) — the elementwise
   // version cost ~3 VALU issues per (pair, dim).  Row norms stage
   // through S.alpha (free until phase E).
-  {
+  const int bsw = nll_bslab(k, d);
+  if (bsw) {
+    // Staged form: nothing lives in S.A yet, so its front holds x' in
+    // column slabs of bsw (a multiple of 16) columns, row stride bsw + 4,
+    // zero-filled past d.  Each wave keeps ALL of its tiles in registers
+    // over the slabs (ascending columns: the MFMA order per tile is that
+    // of the global form) and across the barrier that ends the last
+    // fragment read; only then does the epilogue overwrite the staging
+    // area (the register-tiles-across-a-barrier idiom of phase L).
+    const int ss = bsw + 4;
+    const int nt = (k + 15) / 16;
+    const int ntri = nt * (nt + 1) / 2;
+    const int wave = tid >> 6;
+    const int l16 = lane & 15, kg = lane >> 4;
+    constexpr int MAXT = 5;                 // as in phase L
+    mfma_f32x4 acc[MAXT];                   // compile-time indexed only
+#pragma unroll
+    for (int u = 0; u < MAXT; ++u) acc[u] = {0.f, 0.f, 0.f, 0.f};
+    // row norm of row tid, in scaled_sqnorm's order; the four partials
+    // are carried over the slabs (slab widths are multiples of 4)
+    float n0 = 0.f, n1 = 0.f, n2 = 0.f, n3 = 0.f, nrm = 0.f;
+    for (int s0 = 0; s0 < d; s0 += bsw) {
+      const int sw = d - s0 < bsw ? (d - s0 + 15) & ~15 : bsw;
+      if (s0) __syncthreads();              // reads of the last slab done
+      // 16 lanes per (row, 16-column group): 64-B global segments
+      for (int g = 0; g < sw; g += 16) {
+        const int j = g + (tid & 15), c = s0 + j;
+        for (int a = tid >> 4; a < k; a += WG / 16)
+          S.A[(size_t)a * ss + j] =
+              c < d ? Xe[(size_t)a * d + c] * S.sc[c] : 0.f;
+      }
+      __syncthreads();
+      if (s0 == 0) PH(10);
+      if (tid < k) {
+        const float* xr = S.A + (size_t)tid * ss;
+        int c = 0;
+        // pinned to what the compiler makes of scaled_sqnorm: rounded
+        // squares added to the partials, a fused accumulate in the tail
+        for (; c < sw && s0 + c + 3 < d; c += 4) {
+#pragma clang fp contract(off)
+          const float4 v = *(const float4*)(xr + c);
+          const float q0 = v.x * v.x, q1 = v.y * v.y;
+          const float q2 = v.z * v.z, q3 = v.w * v.w;
+          n0 = n0 + q0; n1 = n1 + q1; n2 = n2 + q2; n3 = n3 + q3;
+        }
+        if (s0 + sw >= d) {                 // last slab: fold, scalar tail
+          nrm = (n0 + n1) + (n2 + n3);
+          for (; s0 + c < d; ++c) nrm = __builtin_fmaf(xr[c], xr[c], nrm);
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < MAXT; ++u) {
+        const int t = wave + u * (WG / 64);
+        if (t >= ntri) continue;
+        int ti, tj;
+        tri_decode(t, ti, tj);
+        const int ia = ti * 16 + l16;       // A-fragment row
+        const int jb = tj * 16 + l16;       // B-fragment column
+        const float* xa = S.A + (size_t)ia * ss + kg;
+        const float* xb = S.A + (size_t)jb * ss + kg;
+        for (int k0 = 0; k0 < sw; k0 += 4 * XCH) {
+          float av[XCH], bv[XCH];
+#pragma unroll
+          for (int v = 0; v < XCH; ++v) {
+            av[v] = ia < k ? xa[k0 + 4 * v] : 0.f;
+            bv[v] = jb < k ? xb[k0 + 4 * v] : 0.f;
+          }
+#pragma unroll
+          for (int v = 0; v < XCH; ++v)
+            if (s0 + k0 + 4 * v < d)
+              acc[u] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[v], bv[v],
+                                                            acc[u], 0, 0, 0);
+        }
+      }
+    }
+    if (tid < k) S.alpha[tid] = nrm;
+    __syncthreads();          // fragment reads complete, norms visible
+#pragma unroll
+    for (int u = 0; u < MAXT; ++u) {
+      const int t = wave + u * (WG / 64);
+      if (t >= ntri) continue;
+      int ti, tj;
+      tri_decode(t, ti, tj);
+      // D map: row = (lane>>4)*4 + r, col = lane&15
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int gi = ti * 16 + kg * 4 + r;
+        const int gj = tj * 16 + l16;
+        if (gi >= k || gj >= k || gj > gi) continue;
+        float q = S.alpha[gi] + S.alpha[gj] - 2.0f * acc[u][r];
+        const float kb = __expf(-(q > 0.f ? q : 0.f));
+        S.A[(size_t)gi * SA + gj] = amp * kb + (gi == gj ? noise : 0.f);
+        if (gi != gj) S.A[(size_t)gj * SA + gi] = kb;   // Kb cache upper
+      }
+    }
+  } else {
+    // no slab fits in S.A, or a single load latency is all there is to
+    // save (nll_bslab): fragments from global X
     for (int a = tid; a < k; a += WG)
       S.alpha[a] = scaled_sqnorm(Xe + (size_t)a * d, S.sc, d);
     __syncthreads();

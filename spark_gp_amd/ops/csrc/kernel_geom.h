@@ -50,10 +50,27 @@ static GEOM_HD inline size_t nll_tsz(int k, int d) {
   return t;
 }
 
+// Phase B of fused_expert_nll_kernel stages the scaled features in the
+// front of the k x SA working buffer, which nothing has written yet, in
+// column slabs: the slab width in columns, a multiple of 16 with rows of
+// stride width + 4 <= SA.  0 selects the global-fragment form, for shapes
+//  - where not even one 16-column slab fits (k < 16), or
+//  - where no wave has more than one tile and no tile more than one
+//    16-index chunk: the global form then pays a single load latency, and
+//    staging would only add a barrier to it ((32, 8) is such a shape).
+static GEOM_HD inline int nll_bslab(int k, int d) {
+  const int nt = (k + 15) / 16;
+  if (nt * (nt + 1) / 2 <= 8 && d <= 16) return 0;
+  const int fit = (((int)geom_sa(k) - 4) / 16) * 16;
+  const int all = (d + 15) & ~15;
+  return all < fit ? all : fit;
+}
+
 // LDS bytes of fused_expert_nll_kernel; region order is NllLds's carve.
-// The scaled features are not kept in LDS (phases B and H read their MFMA
-// fragments from global X), which is what lets three experts share a CU
-// at k = 100: 53 344 B against floor(160 KiB / 3) = 54 613 B.
+// The scaled features have no region of their own: phase B stages them
+// inside A before anything else is written there (nll_bslab) and phase H
+// reads its MFMA fragments from global X.  That is what lets three experts
+// share a CU at k = 100: 53 344 B against floor(160 KiB / 3) = 54 613 B.
 static GEOM_HD inline size_t nll_lds_bytes(int k, int d) {
   size_t off = 0;
   off += a16(sizeof(double) * 10);                      // red + misc
