@@ -47,8 +47,10 @@ if clk[:, 10].max() > 0:
     print(f"  B, of which staging the first slab: "
           f"{((clk[:, 10] - clk[:, 1]) / FREQ * 1e6).mean():8.2f} us")
 sub = clk[:, 12:18].mean(0) / FREQ * 1e6
-subnames = ["phase1 diag-pre", "phase2 wall", "wave0 span",
-            "waves1-7 span", "C2 panel solve", "D off-diag trtri"]
+# phase2 wall = the wave-0 q-loop (with waves 1-7's update beside it) plus
+# the all-thread assembly of the 32x32 inverse behind the q-loop's barrier
+subnames = ["phase1 diag-pre", "phase2 wall", "wave0 q-loop",
+            "waves1-7 update", "C2 panel solve", "D off-diag trtri"]
 print("C/D sub-phases (accumulated over J, mean per expert):")
 for n, v in zip(subnames, sub):
     print(f"  {n:>18}: {v:8.2f} us")

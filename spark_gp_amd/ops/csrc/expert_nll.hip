@@ -13,17 +13,20 @@
 //      sqdist is q = n_a + n_b - 2 x'.a' over pre-SCALED coordinates on
 //      f32 MFMA tiles (the gradient contraction runs in scaled space and
 //      is de-scaled by s2 at output)
-//   C  blocked right-looking Cholesky, IN PLACE, with look-ahead: per
-//      8-column sub-block q of each 32-column block, wave 0 factors AND
-//      inverts the 8x8 sub-diagonal (row-per-lane on 8 lanes, cross-lane
-//      traffic via v_readlane broadcasts from STATIC lanes; branchless
-//      frexp-accumulated log-det) WHILE waves 1-7 apply chunk q of the
-//      previous panel's rank-32 trailing update; then ALL 512 threads do
-//      the intra-block panel/trailing and, after the 4 sub-blocks, the
-//      block back-substitution assembling the 32x32 inverse.  The panel
-//      solve is a dense GEMM against the inverted diagonal.
-//      fp32; fp64 logdet.  (Design history and negative results:
-//      profiles/PROFILES.md and TODO.md item 1.)
+//   C  blocked right-looking Cholesky, IN PLACE, with look-ahead: the
+//      q-loop over the 8-column sub-blocks of each 32-column diagonal
+//      block belongs to wave 0 alone, with no workgroup barrier inside:
+//      per q it factors AND inverts the 8x8 sub-diagonal (row-per-lane on
+//      8 lanes, cross-lane traffic via v_readlane broadcasts from STATIC
+//      lanes; branchless frexp-accumulated log-det), forms the intra-block
+//      panel one row per lane and applies the intra-block trailing update,
+//      ordered at wave scope (wave_lds_sync) — WHILE waves 1-7 apply the
+//      previous panel's rank-32 trailing update in one pass.  One barrier
+//      ends the q-loop on every path, a failed pivot included; then ALL
+//      512 threads run the block back-substitution assembling the 32x32
+//      inverse.  The panel solve is a dense GEMM against the inverted
+//      diagonal.  fp32; fp64 logdet.  (Design history and negative
+//      results: profiles/PROFILES.md and TODO.md item 1.)
 //   D  blocked in-place triangular inverse of the off-diagonal blocks
 //      (right-to-left column blocks, rows fully parallel:
 //       V_IJ = -(sum_{K>J} V_IK L_KJ) L_JJ^-1).

@@ -74,6 +74,23 @@ __device__ inline float dotv(const float* p, const float* q, int c0,
   return s;
 }
 
+// dotv(p, q, 0, 8) spelled out as the compiler builds dotv's float4 body
+// where the length is a run-time value (the all-thread intra-block
+// trailing update this replaces): rounded products added to the four
+// partials (v_pk_mul_f32, v_pk_add_f32), not fused; then dotv's fold.
+__device__ inline float dot8_unfused(const float* p, const float* q) {
+#pragma clang fp contract(off)
+  const float4 a0 = *(const float4*)p, b0 = *(const float4*)q;
+  const float4 a1 = *(const float4*)(p + 4), b1 = *(const float4*)(q + 4);
+  const float m0 = a0.x * b0.x, m1 = a0.y * b0.y;
+  const float m2 = a0.z * b0.z, m3 = a0.w * b0.w;
+  const float n0 = a1.x * b1.x, n1 = a1.y * b1.y;
+  const float n2 = a1.z * b1.z, n3 = a1.w * b1.w;
+  const float x = (0.f + m0) + n0, y = (0.f + m1) + n1;
+  const float z = (0.f + m2) + n2, w = (0.f + m3) + n3;
+  return 0.f + ((x + y) + (z + w));
+}
+
 // Vectorized-p x strided-q dot: p 16-B aligned at index 0, q any stride.
 __device__ inline float dotm(const float* p, const float* q, int sq,
                              int c0, int c1) {
@@ -108,6 +125,18 @@ __device__ inline float dot4(const float* p, int sp, const float* q, int sq,
   return (s0 + s1) + (s2 + s3);
 }
 
+// Orders one wave's LDS writes before its later LDS reads from other lanes,
+// with no workgroup barrier: the DS operations of one wave complete in
+// issue order, so all that is needed is that the compiler keeps them on
+// their sides of this point (wavefront-scope fence + wave_barrier) and
+// that the writes have retired (lgkmcnt).  The wave must be converged.
+__device__ inline void wave_lds_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
 // In place on the lower triangle of Abuf (k x k, row stride SA):
 // K -> L -> V = L^{-1} (lower).  Strict upper of Abuf is never touched.
 // log|K| accumulates into misc[0]; *bad set to 1 (indefinite) or 2
@@ -120,7 +149,9 @@ __device__ inline void chol_invert_lower(float* Abuf, float* Tbuf,
                                          double* misc,
                                          unsigned long long* jclk = nullptr) {
   // jclk (profiling only): accumulated cycles into
-  //   [0] phase1  [1] phase2 wall  [2] wave0 span  [3] waves1-7 span
+  //   [0] phase1  [1] phase2 wall (q-loop + inverse assembly)
+  //   [2] wave 0's q-loop span (clocked by thread 0)
+  //   [3] waves 1-7's update span (clocked by thread 64)
   //   [4] C2 panel solve  [5] D off-diag trtri
   // tid passes through an empty asm at the top of every block-column
   // iteration: values derived from it are then recomputed per iteration
@@ -161,29 +192,35 @@ __device__ inline void chol_invert_lower(float* Abuf, float* Tbuf,
     }
     if (jclk && (tid == 0 || tid == 64)) jt1 = wall_clock64();
 
-    // phase2, restructured (round-1 profiling: the old wave-0-only
-    // version spent 86 us/expert on one wave while waves 1-7 idled 5 us):
-    // per 8-column sub-block q, wave 0 runs the shfl factor+trtri while
-    // waves 1-7 process chunk q of panel J-1's update to the rows below
-    // this column block; then ALL 512 threads apply the intra-block
-    // panel/trailing for q.  The 32x32 inverse assembly afterwards also
-    // runs on all threads.  8x8 inverses live in T[0..256); T[256..448)
-    // is shell scratch.
+    // phase2: the q-loop over the 8-column sub-blocks of the diagonal
+    // block is wave 0's job alone, with no workgroup barrier inside it:
+    // per q the register factor + trtri8, the intra-block panel (one
+    // lane per panel row) and the intra-block trailing update (two
+    // elements per lane in flight); dependent LDS writes and reads are
+    // ordered by wave_lds_sync().  Meanwhile waves 1-7 apply panel J-1's
+    // update to the rows below this column block in one pass.  One
+    // __syncthreads() ends the q-loop, executed by every wave whatever
+    // the pivots do: on a failed pivot wave 0 sets *bad, skips its
+    // remaining sub-blocks and falls through to it.  The 32x32 inverse
+    // assembly behind it runs on all threads (in wave 0 alone it took as
+    // long and lengthened the short shapes: profiles/PROFILES.md round 6).
+    // 8x8 inverses live in T[0..256); T[256..448) is shell scratch.
     const int nq = (bs + 7) / 8;
     float* Vq = Tbuf;               // [nq][8][8]
     float* TS = Tbuf + 256;         // shell scratch [3][8][8]
     const int t0r = jb + bs;        // first row below this column block
     const int nrp = k - t0r;
     const int ntri_rest = nrp * (nrp + 1) / 2;
-    for (int q = 0; q < nq; ++q) {
-      const int qb = q * 8;
-      const int sbs = min(8, bs - qb);
-      if (tid < 64) {
-        // static priority for the serial factor wave: its dependent
-        // shfl/VALU chain is the block's critical path while waves 1-7
-        // stream trailing updates — give it the issue-arbitration edge
-        // (MI355X_MICROARCH.md "Two waves per SIMD", item 4)
-        __builtin_amdgcn_s_setprio(1);
+    if (tid < 64) {
+      // static priority for the serial diagonal-block wave: its dependent
+      // chain is the block's critical path while waves 1-7 stream trailing
+      // updates — give it the issue-arbitration edge
+      // (MI355X_MICROARCH.md "Two waves per SIMD", item 4)
+      __builtin_amdgcn_s_setprio(1);
+      int w0ok = 1;                  // wave-uniform: no pivot failed yet
+      for (int q = 0; q < nq; ++q) {
+        const int qb = q * 8;
+        const int sbs = min(8, bs - qb);
         {
           // 8x8 factor + trtri on lanes 0..7, ROW j per lane, cross-lane
           // traffic via bcast_lane (every source lane is a compile-time
@@ -267,6 +304,9 @@ __device__ inline void chol_invert_lower(float* Abuf, float* Tbuf,
 #pragma unroll
             for (int i = 0; i < 8; ++i) Vq[q * 64 + i * 8 + j] = v[i];
           }
+          // ok is the same in every lane (every pivot is a broadcast);
+          // the exit decision is taken on lane 0's copy in an SGPR
+          w0ok = __builtin_amdgcn_readlane((int)ok, 0);
           if (lane == 0) {
             if (!ok) {
               if (*bad == 0) *bad = nonfin ? 2 : 1;  // sticky: first cause
@@ -276,70 +316,97 @@ __device__ inline void chol_invert_lower(float* Abuf, float* Tbuf,
             }
           }
         }
-        __builtin_amdgcn_s_setprio(0);
-      } else if (J > 0) {
-        // waves 1-7, chunk q (strided by nq, so any nq covers everything):
-        // previous panel's update to (a) the panel rows of column-block J
-        // and (b) the remaining trailing triangle
-        for (int f = (tid - 64) + q * (WG - 64); f < nrp * bs;
-             f += (WG - 64) * nq) {
-          const int r = f / bs, c = f - r * bs;
-          const int i = t0r + r, cc = jb + c;
-          Abuf[(size_t)i * SA + cc] -=
-              dotv(Abuf + (size_t)i * SA + pj,
-                   Abuf + (size_t)cc * SA + pj, 0, NB);
-        }
-        for (int f = (tid - 64) + q * (WG - 64); f < ntri_rest;
-             f += (WG - 64) * nq) {
-          int a, b;
-          tri_decode(f, a, b);
-          const int i = t0r + a, c = t0r + b;
-          Abuf[(size_t)i * SA + c] -=
-              dotv(Abuf + (size_t)i * SA + pj,
-                   Abuf + (size_t)c * SA + pj, 0, NB);
+        if (!w0ok) break;            // wave-uniform; on to the block barrier
+        wave_lds_sync();             // L write-back and Vq visible
+        // intra-block panel P = A * Vq^T for q: one lane per panel row,
+        // the row's 8 inputs in registers, so the row is overwritten by
+        // its only reader.  pr > 0 implies a full sub-block (sbs == 8).
+        const int p0 = qb + sbs;     // first panel row (local)
+        const int pr = bs - p0;      // panel rows (<= 24)
+        if (pr > 0) {
+          if (lane < pr) {
+            float* ap = D + (size_t)(p0 + lane) * SA + qb;
+            const float4 a0 = *(const float4*)ap;
+            const float4 a1 = *(const float4*)(ap + 4);
+            const float ar[8] = {a0.x, a0.y, a0.z, a0.w,
+                                 a1.x, a1.y, a1.z, a1.w};
+            const float* vr = Vq + q * 64;
+            float o[8];
+#pragma unroll
+            for (int c = 0; c < 8; ++c) {
+              float sacc = 0.f;
+#pragma unroll
+              for (int t = 0; t <= c; ++t)
+                sacc = __builtin_fmaf(ar[t], vr[c * 8 + t], sacc);
+              o[c] = sacc;
+            }
+            *(float4*)ap = make_float4(o[0], o[1], o[2], o[3]);
+            *(float4*)(ap + 4) = make_float4(o[4], o[5], o[6], o[7]);
+          }
+          wave_lds_sync();           // panel rows visible
+          // trailing: lower incl diag of the remaining pr rows of this
+          // block, each element less its length-8 dot over the panel
+          // columns (dotv's order of summation).  Rows r and pr-1-r
+          // share one line of a ceil(pr/2) x (pr+1) grid, which takes
+          // one multiply to decode; a lane holds two elements' loads in
+          // flight.  For odd pr the middle row is its own partner and
+          // the slots past its diagonal are void.
+          const int wd = pr + 1, tot = ((pr + 1) >> 1) * wd;
+          const float rwd = 1.f / (float)wd;
+          for (int f0 = lane; f0 < tot; f0 += 128) {
+            float* tp[2];
+            const float *pa[2], *pb[2];
+            bool on[2];
+#pragma unroll
+            for (int u = 0; u < 2; ++u) {
+              const int f = f0 + 64 * u;
+              // f < 512 and wd <= 25: (f + 0.5) / wd is at least 0.02
+              // from an integer, the float quotient exact after the cast
+              const int r = (int)(((float)f + 0.5f) * rwd);
+              const int c = f - r * wd;
+              const bool lo = c <= r;
+              on[u] = f < tot && (lo || pr - 1 - r != r);
+              const int a = on[u] ? (lo ? r : pr - 1 - r) : 0;
+              const int b = on[u] ? (lo ? c : c - r - 1) : 0;
+              tp[u] = D + (size_t)(p0 + a) * SA + p0 + b;
+              pa[u] = D + (size_t)(p0 + a) * SA + qb;
+              pb[u] = D + (size_t)(p0 + b) * SA + qb;
+            }
+            // both dots before either store: the loads issue together
+            const float s0 = dot8_unfused(pa[0], pb[0]);
+            const float s1 = dot8_unfused(pa[1], pb[1]);
+            if (on[0]) *tp[0] -= s0;
+            if (on[1]) *tp[1] -= s1;
+          }
+          wave_lds_sync();           // next sub-block's inputs visible
         }
       }
-      __syncthreads();
-      if (*bad) break;               // uniform: read after the barrier
-      // intra-block panel P = A * Vq^T and trailing for q, ALL threads
-      const int p0 = qb + sbs;       // first panel row (local)
-      const int pr = bs - p0;        // panel rows
-      if (pr > 0) {
-        for (int f = tid; f < pr * 8; f += WG) {
-          const int r = f >> 3, c = f & 7;
-          if (c >= sbs) continue;
-          float sacc = 0.f;
-          const float* ar = D + (size_t)(p0 + r) * SA + qb;
-          const float* vr = Vq + q * 64 + c * 8;
-          for (int t = 0; t <= c; ++t) sacc += ar[t] * vr[t];
-          TS[f] = sacc;              // hold row piece until all reads done
-        }
-        __syncthreads();
-        for (int f = tid; f < pr * 8; f += WG) {
-          const int r = f >> 3, c = f & 7;
-          if (c >= sbs) continue;
-          D[(size_t)(p0 + r) * SA + qb + c] = TS[f];
-        }
-        __syncthreads();
-        // trailing: lower incl diag of remaining rows of this block
-        const int ntri = pr * (pr + 1) / 2;
-        for (int f = tid; f < ntri; f += WG) {
-          int a, b;
-          tri_decode(f, a, b);
-          const int i = p0 + a, c = p0 + b;
-          Abuf[(size_t)(jb + i) * SA + jb + c] -=
-              dotv(D + (size_t)i * SA + qb, D + (size_t)c * SA + qb,
-                   0, sbs);
-        }
-        __syncthreads();
+      __builtin_amdgcn_s_setprio(0);
+      if (jclk && tid == 0) jclk[2] += wall_clock64() - jt1;
+    } else if (J > 0) {
+      // waves 1-7, one pass: previous panel's update to (a) the panel
+      // rows of column-block J and (b) the remaining trailing triangle
+      for (int f = tid - 64; f < nrp * bs; f += WG - 64) {
+        const int r = f / bs, c = f - r * bs;
+        const int i = t0r + r, cc = jb + c;
+        Abuf[(size_t)i * SA + cc] -=
+            dotv(Abuf + (size_t)i * SA + pj,
+                 Abuf + (size_t)cc * SA + pj, 0, NB);
       }
+      for (int f = tid - 64; f < ntri_rest; f += WG - 64) {
+        int a, b;
+        tri_decode(f, a, b);
+        const int i = t0r + a, c = t0r + b;
+        Abuf[(size_t)i * SA + c] -=
+            dotv(Abuf + (size_t)i * SA + pj,
+                 Abuf + (size_t)c * SA + pj, 0, NB);
+      }
+      if (jclk && tid == 64) jclk[3] += wall_clock64() - jt1;
     }
-    unsigned long long at0 = 0;
-    if (jclk && tid == 0) {
-      at0 = wall_clock64();
-      jclk[2] += at0 - jt1;          // q-loop wall (factor+chunks+intra)
-    }
-    if (*bad == 0) {
+    // the q-loop's one barrier: every wave arrives here whatever happened
+    // above (no workgroup barrier and no return inside either branch)
+    __syncthreads();
+    if (*bad == 0) {                 // uniform: read after the barrier
       // ---- assemble V_JJ (32x32 inverse) from the 8x8 inverses --------
       // column-blocks Jq descending; all target blocks of a column in
       // parallel through TS; ALL threads
@@ -380,11 +447,9 @@ __device__ inline void chol_invert_lower(float* Abuf, float* Tbuf,
           const int gi = jb8 + i, gj = jb8 + j;
           if (gi < bs && gj <= gi) D[(size_t)gi * SA + gj] = Vq[Jq * 64 + f];
         }
-        __syncthreads();
+        __syncthreads();             // the last one ends the block
       }
     }
-    if (jclk && tid == 0) jclk[3] += wall_clock64() - at0;  // assembly wall
-    __syncthreads();
     if (jclk && tid == 0) {
       const unsigned long long t2 = wall_clock64();
       jclk[0] += jt1 - jt0;
