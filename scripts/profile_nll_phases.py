@@ -46,11 +46,13 @@ for i in range(9):
 if clk[:, 10].max() > 0:
     print(f"  B, of which staging the first slab: "
           f"{((clk[:, 10] - clk[:, 1]) / FREQ * 1e6).mean():8.2f} us")
-sub = clk[:, 12:18].mean(0) / FREQ * 1e6
-# phase2 wall = the wave-0 q-loop (with waves 1-7's update beside it) plus
-# the all-thread assembly of the 32x32 inverse behind the q-loop's barrier
+sub = clk[:, 12:19].mean(0) / FREQ * 1e6
+# phase2 wall = the wave-0 q-loop (with waves 1-7's update beside it), wave
+# 0's MFMA assembly of the 32x32 inverse straight behind it (slot 18, jclk
+# [6] of chol_invert_lower) and the barrier that ends the phase
 subnames = ["phase1 diag-pre", "phase2 wall", "wave0 q-loop",
-            "waves1-7 update", "C2 panel solve", "D off-diag trtri"]
+            "waves1-7 update", "C2 panel solve", "D off-diag trtri",
+            "wave0 inverse assembly"]
 print("C/D sub-phases (accumulated over J, mean per expert):")
 for n, v in zip(subnames, sub):
     print(f"  {n:>18}: {v:8.2f} us")

@@ -16,15 +16,16 @@
 //   C  blocked right-looking Cholesky, IN PLACE, with look-ahead: the
 //      q-loop over the 8-column sub-blocks of each 32-column diagonal
 //      block belongs to wave 0 alone, with no workgroup barrier inside:
-//      per q it factors AND inverts the 8x8 sub-diagonal (row-per-lane on
-//      8 lanes, cross-lane traffic via v_readlane broadcasts from STATIC
-//      lanes; branchless frexp-accumulated log-det), forms the intra-block
-//      panel one row per lane and applies the intra-block trailing update,
-//      ordered at wave scope (wave_lds_sync) — WHILE waves 1-7 apply the
-//      previous panel's rank-32 trailing update in one pass.  One barrier
-//      ends the q-loop on every path, a failed pivot included; then ALL
-//      512 threads run the block back-substitution assembling the 32x32
-//      inverse.  The panel solve is a dense GEMM against the inverted
+//      per q it factors AND inverts the 8x8 sub-diagonal in one 8-step
+//      elimination (row-per-lane on 8 lanes, cross-lane traffic via
+//      v_readlane broadcasts from STATIC lanes; branchless
+//      frexp-accumulated log-det), forms the intra-block panel one row per
+//      lane and applies the intra-block trailing update, ordered at wave
+//      scope (wave_lds_sync); behind the loop it assembles the 32x32
+//      inverse from the 8x8 inverses by recursive doubling on f32 MFMA —
+//      WHILE waves 1-7 apply the previous panel's rank-32 trailing update
+//      in one pass.  One barrier ends this on every path, a failed pivot
+//      included.  The panel solve is a dense GEMM against the inverted
 //      diagonal.  fp32; fp64 logdet.  (Design history and negative
 //      results: profiles/PROFILES.md and TODO.md item 1.)
 //   D  blocked in-place triangular inverse of the off-diagonal blocks

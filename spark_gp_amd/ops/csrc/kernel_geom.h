@@ -39,8 +39,10 @@ static GEOM_HD inline size_t geom_dp4(int d) {
 }
 
 // temp buffer of fused_expert_nll_kernel, in floats: only the terms its own
-// phases use (geom_tsz's 32*SA term is laplace.hip's).  Vq/TS of the 8x8
-// factor: 448; the C2 panel copy and D's U: (k-32) rows of stride 36; H's
+// phases use (geom_tsz's 32*SA term is laplace.hip's).  The 8x8 inverses
+// Vq of a diagonal block take 256 of a floor of 448 (the rest was the
+// earlier assembly's scratch; the floor stays, and with it the LDS plan
+// and chol_invert_lower's contract); the C2 panel copy and D's U: (k-32) rows of stride 36; H's
 // per-row-tile partials: ceil(k/16)*d.
 static GEOM_HD inline size_t nll_tsz(int k, int d) {
   size_t t = 448;

@@ -137,11 +137,123 @@ __device__ inline void wave_lds_sync() {
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
+// The inverse of one diagonal block (bs <= 32 rows at D, row stride SA)
+// assembled from its nq = ceil(bs/8) inverted 8x8 sub-blocks Vq[q][8][8]
+// (row-major, zero above the diagonal, identity-padded where the last
+// sub-block is short) and the sub-diagonal blocks of L still in D, by
+// recursive doubling on v_mfma_f32_16x16x4_f32 (exact f32):
+//   level 1: V10 = -V1 (L10 V0) and V32 = -V3 (L32 V2), the two pairs
+//            block-diagonal in one 16x16 tile;
+//   level 2: V_HL = -V_HH (L_HL V_LL) on the 16x16 halves.
+// Each level is two dependent products of 4 MFMAs.  Both operands of a
+// product take k = 4 * (lane >> 4) + s at MFMA step s, so the B value a
+// lane owes the second product is its own accumulator register s of the
+// first (C layout: row 4 * (lane >> 4) + s, column lane & 15): the
+// intermediate never passes through LDS.  Level 1's tile carries pair 0 in
+// rows 8..15 x columns 0..7 and pair 1 in rows 0..7 x columns 8..15, which
+// puts V10 where level 2's V_LL fragment wants it, again in the lane's own
+// registers; only V32 comes back from D.  Rows and columns past bs are
+// masked to zero and never stored.  One converged wave; the caller orders
+// the q-loop's LDS writes before and this function's after.
+__device__ inline void assemble_diag_inverse(float* D, const int SA,
+                                             const float* Vq, const int bs,
+                                             const int nq, const int lane) {
+  const int fl = lane & 15, kg = lane >> 4;
+  const int fp = fl >> 3, f7 = fl & 7;
+  // Every fragment that no product feeds is fetched up front, so that the
+  // LDS round trips overlap and the MFMA chain waits once.  A masked
+  // element reads index 0 (always inside the buffer) and is then zeroed: a
+  // load under a lane condition would be issued, and waited for, in its
+  // own branch right before the MFMA that takes it.
+  float dg[4];                             // Vq, for the diagonal blocks
+#pragma unroll
+  for (int u = 0; u < 4; ++u) dg[u] = Vq[lane + 64 * u];
+  float a1[4], b1[4], a2[4], a3[4], vd[4], a4[4];
+  const int lrow = 16 * fp + 8 + f7;       // row of L_{2p+1,2p}, p = fp
+  const bool hrow = 16 + fl < bs;          // row of L_HL (implies nq >= 3)
+#pragma unroll
+  for (int s = 0; s < 4; ++s) {
+    const int kk = 4 * kg + s, k7 = kk & 7, kp = kk >> 3;
+    const bool c1 = kp == fp && lrow < bs;
+    const bool c2 = kp == fp && 2 * fp < nq;
+    const bool c3 = kp != fp && 2 * kp + 1 < nq;
+    const bool c4 = kp == fp && 2 + fp < nq;
+    const float x1 = D[c1 ? (size_t)lrow * SA + 16 * fp + k7 : 0];
+    const float x2 = Vq[c2 ? (2 * fp) * 64 + k7 * 8 + f7 : 0];
+    const float x3 = Vq[c3 ? (2 * kp + 1) * 64 + f7 * 8 + k7 : 0];
+    const float x4 = D[hrow ? (size_t)(16 + fl) * SA + kk : 0];
+    const float x5 = Vq[c4 ? (2 + fp) * 64 + f7 * 8 + k7 : 0];
+    vd[s] = Vq[kp * 64 + k7 * 8 + f7];     // V0 / V1: nq >= 2 here or unused
+    a1[s] = c1 ? x1 : 0.f;                 // blockdiag(L10, L32)[fl][kk]
+    b1[s] = c2 ? x2 : 0.f;                 // blockdiag(V0, V2)[kk][fl]
+    a2[s] = c3 ? x3 : 0.f;                 // V_{2p+1}[f7][k7], p = kp = 1 - fp
+    a3[s] = hrow ? x4 : 0.f;               // L_HL[fl][kk]
+    a4[s] = c4 ? x5 : 0.f;                 // diagonal blocks of V_HH[fl][kk]
+  }
+  // the diagonal 8x8 blocks of D <- Vq: L's diagonal blocks have no reader
+  // left, and no product reads D there
+#pragma unroll
+  for (int u = 0; u < 4; ++u) {
+    const int i = lane >> 3, j = lane & 7; // sub-block u, element (i, j)
+    const int gi = u * 8 + i;
+    if (gi < bs && j <= i) D[(size_t)gi * SA + u * 8 + j] = dg[u];
+  }
+  if (nq < 2) return;
+  // level 1.  W[kk][j] = (L_{2p+1,2p} V_{2p})[kk & 7][j & 7], p = kk>>3 =
+  // j>>3; R[i][j] = sum_kk V_{2p+1}[i & 7][kk & 7] W[kk][j], p = kk>>3 =
+  // 1 - i>>3: pair p's product sits in rows of 1 - p, columns of p
+  mfma_f32x4_t w = {0.f, 0.f, 0.f, 0.f};
+  mfma_f32x4_t r1 = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int s = 0; s < 4; ++s)
+    w = __builtin_amdgcn_mfma_f32_16x16x4f32(a1[s], b1[s], w, 0, 0, 0);
+#pragma unroll
+  for (int s = 0; s < 4; ++s)
+    r1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a2[s], w[s], r1, 0, 0, 0);
+#pragma unroll
+  for (int s = 0; s < 4; ++s) {
+    const int row = 4 * kg + s;
+    const int gr = 16 * fp + 8 + (row & 7);
+    if ((row >> 3) != fp && gr < bs)
+      D[(size_t)gr * SA + 16 * fp + f7] = -r1[s];
+  }
+  if (nq < 3) return;
+  // level 2.  W2 = L_HL V_LL; V_LL[kk][j]: its diagonal blocks are V0 and
+  // V1, its lower-left block V10 = -r1[s] of this lane
+  mfma_f32x4_t w2 = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int s = 0; s < 4; ++s) {
+    const int kp = (4 * kg + s) >> 3;
+    const float bv = (kp == fp) ? vd[s] : (kp > fp ? -r1[s] : 0.f);
+    w2 = __builtin_amdgcn_mfma_f32_16x16x4f32(a3[s], bv, w2, 0, 0, 0);
+  }
+  // R2 = V_HH W2; V_HH[i][kk]: diagonal blocks V2 and V3 (a4), lower-left
+  // block V32, which level 1 has just stored
+  wave_lds_sync();
+  float a5[4];
+#pragma unroll
+  for (int s = 0; s < 4; ++s) {
+    const int kk = 4 * kg + s, k7 = kk & 7, kp = kk >> 3;
+    const bool c5 = fp > kp && 24 + f7 < bs;
+    const float x = D[c5 ? (size_t)(24 + f7) * SA + 16 + k7 : 0];
+    a5[s] = c5 ? x : a4[s];
+  }
+  mfma_f32x4_t r2 = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int s = 0; s < 4; ++s)
+    r2 = __builtin_amdgcn_mfma_f32_16x16x4f32(a5[s], w2[s], r2, 0, 0, 0);
+#pragma unroll
+  for (int s = 0; s < 4; ++s) {
+    const int gr = 16 + 4 * kg + s;
+    if (gr < bs) D[(size_t)gr * SA + fl] = -r2[s];
+  }
+}
+
 // In place on the lower triangle of Abuf (k x k, row stride SA):
 // K -> L -> V = L^{-1} (lower).  Strict upper of Abuf is never touched.
 // log|K| accumulates into misc[0]; *bad set to 1 (indefinite) or 2
 // (non-finite pivot) on breakdown.  Tbuf: >= max((k-32)*36, 448) floats
-// scratch, 16-B aligned; SA must be a multiple of 4 (vectorized dots).
+// scratch, 16-B aligned (the diagonal block uses T[0..256)); SA must be a multiple of 4 (vectorized dots).
 // All WG threads must call (contains __syncthreads).
 __device__ inline void chol_invert_lower(float* Abuf, float* Tbuf,
                                          const int k, const int SA,
@@ -153,6 +265,7 @@ __device__ inline void chol_invert_lower(float* Abuf, float* Tbuf,
   //   [2] wave 0's q-loop span (clocked by thread 0)
   //   [3] waves 1-7's update span (clocked by thread 64)
   //   [4] C2 panel solve  [5] D off-diag trtri
+  //   [6] wave 0's inverse-assembly span behind the q-loop (thread 0)
   // tid passes through an empty asm at the top of every block-column
   // iteration: values derived from it are then recomputed per iteration
   // (a few VALU ops) instead of being hoisted and kept live across the
@@ -194,20 +307,22 @@ __device__ inline void chol_invert_lower(float* Abuf, float* Tbuf,
 
     // phase2: the q-loop over the 8-column sub-blocks of the diagonal
     // block is wave 0's job alone, with no workgroup barrier inside it:
-    // per q the register factor + trtri8, the intra-block panel (one
-    // lane per panel row) and the intra-block trailing update (two
-    // elements per lane in flight); dependent LDS writes and reads are
-    // ordered by wave_lds_sync().  Meanwhile waves 1-7 apply panel J-1's
-    // update to the rows below this column block in one pass.  One
-    // __syncthreads() ends the q-loop, executed by every wave whatever
+    // per q the register factor-and-inverse of the 8x8 sub-block, the
+    // intra-block panel (one lane per panel row) and the intra-block
+    // trailing update (two elements per lane in flight); dependent LDS
+    // writes and reads are ordered by wave_lds_sync().  Straight behind
+    // the loop wave 0 assembles the block's inverse from the 8x8 inverses
+    // (assemble_diag_inverse: 16 MFMAs and one more wave_lds_sync(); that
+    // short, it costs less there than behind the barrier, where the
+    // column-by-column assembly it replaces had to stay:
+    // profiles/PROFILES.md rounds 6 and 7).  Meanwhile waves 1-7 apply
+    // panel J-1's update to the rows below this column block in one pass.
+    // One __syncthreads() ends phase 2, executed by every wave whatever
     // the pivots do: on a failed pivot wave 0 sets *bad, skips its
-    // remaining sub-blocks and falls through to it.  The 32x32 inverse
-    // assembly behind it runs on all threads (in wave 0 alone it took as
-    // long and lengthened the short shapes: profiles/PROFILES.md round 6).
-    // 8x8 inverses live in T[0..256); T[256..448) is shell scratch.
+    // remaining sub-blocks and the assembly and falls through to it.
+    // 8x8 inverses live in T[0..256).
     const int nq = (bs + 7) / 8;
     float* Vq = Tbuf;               // [nq][8][8]
-    float* TS = Tbuf + 256;         // shell scratch [3][8][8]
     const int t0r = jb + bs;        // first row below this column block
     const int nrp = k - t0r;
     const int ntri_rest = nrp * (nrp + 1) / 2;
@@ -222,7 +337,7 @@ __device__ inline void chol_invert_lower(float* Abuf, float* Tbuf,
         const int qb = q * 8;
         const int sbs = min(8, bs - qb);
         {
-          // 8x8 factor + trtri on lanes 0..7, ROW j per lane, cross-lane
+          // 8x8 factor and inverse on lanes 0..7, ROW j per lane, cross-lane
           // traffic via bcast_lane (every source lane is a compile-time
           // constant, so no LDS-pipe round trip).  Row-per-lane keeps every
           // runtime-varying access at a STATIC register index: the rank-1
@@ -231,13 +346,23 @@ __device__ inline void chol_invert_lower(float* Abuf, float* Tbuf,
           // version needed l[j] with a runtime lane index, which compiles
           // to an 8-deep v_cmp/cndmask select chain per pivot step.
           // Lanes 8..63 compute duplicates and are masked off every store.
+          //
+          // One 8-step elimination gives both factors: the multipliers
+          // that reduce the sub-block are applied to an identity alongside
+          // (inv, row j of it), which leaves inv = Lu^-1 of the unit-lower
+          // factor, so V[j][c] = rs_j * inv[c]; and L[j][ss] = row[ss] * rs
+          // at step ss.  A step's two updates are independent, so its
+          // chain is gather, rsqrt, two multiplies, one FMA.
           const int j = lane & 7;
           float row[8];                 // this lane's row: row[c] = m[j][c]
+          float inv[8];                 // row j of the running Lu^-1
 #pragma unroll
-          for (int c = 0; c < 8; ++c)
+          for (int c = 0; c < 8; ++c) {
             row[c] = (j < sbs && c < sbs && c <= j)
                          ? D[(size_t)(qb + j) * SA + qb + c]
                          : (c == j ? 1.f : 0.f);
+            inv[c] = (c == j) ? 1.f : 0.f;
+          }
           bool ok = true, nonfin = false;
           // log|sub-block| via one logf at the end: accumulate the pivot
           // mantissa product and exponent sum (branchless — a per-step
@@ -246,17 +371,21 @@ __device__ inline void chol_invert_lower(float* Abuf, float* Tbuf,
           float mprod = 1.f;
           int expsum = 0;
           float myrs = 1.f;             // this row's pivot 1/sqrt
-          float rsv = 1.f;
 #pragma unroll
           for (int ss = 0; ss < 8; ++ss) {
-            float l[8];                 // column ss: l[c] = lane c's row[ss]
+            // column ss of the Schur complement, by symmetry also pivot
+            // row ss: l[c] = lane c's row[ss]; pinv: row ss of inv, final
+            // since step ss-1 (its diagonal is 1)
+            float l[8], pinv[8];
 #pragma unroll
-            for (int c = 0; c < 8; ++c) l[c] = bcast_lane(row[ss], c);
+            for (int c = ss; c < 8; ++c) l[c] = bcast_lane(row[ss], c);
+#pragma unroll
+            for (int c = 0; c < ss; ++c) pinv[c] = bcast_lane(inv[c], ss);
             const float piv = l[ss];
             if (ss < sbs) {
               const bool fin = isfinite(piv);
               // classify only the FIRST failure (nonfin wins only if it
-              // happens while still ok)
+              // happens while still ok), on piv, before rs is used
               nonfin = nonfin || (ok && !fin);
               ok = ok && fin && (piv > 0.f);
               mprod *= __builtin_amdgcn_frexp_mantf(piv);
@@ -264,45 +393,28 @@ __device__ inline void chol_invert_lower(float* Abuf, float* Tbuf,
             }
             const float rs = rsqrtf(piv);
             if (j == ss) myrs = rs;
-            // subtract l_j*l_c = (rs*row[ss]) * (rs*l[c]) for c > ss; rows
-            // j <= ss get w = 0 (their updates ended at step j)
-            const float w = (j > ss) ? rs * row[ss] : 0.f;
+            // rows j <= ss get m = 0 (their updates ended at step j)
+            const float m = (j > ss) ? row[ss] * (rs * rs) : 0.f;
 #pragma unroll
-            for (int c = ss + 1; c < 8; ++c) row[c] -= (rs * l[c]) * w;
+            for (int c = ss + 1; c < 8; ++c)
+              row[c] = __builtin_fmaf(-m, l[c], row[c]);
+#pragma unroll
+            for (int c = 0; c < ss; ++c)
+              inv[c] = __builtin_fmaf(-m, pinv[c], inv[c]);
+            if (j > ss) inv[ss] = -m;
+            row[ss] *= rs;              // L[j][ss]
           }
-          // deferred column scaling: L[j][c] = row[c] * rs_c; gather the
-          // rs vector from the diagonal lanes (rs_c = lane c's myrs)
 #pragma unroll
-          for (int c = 0; c < 8; ++c) {
-            rsv = bcast_lane(myrs, c);
-            row[c] *= rsv;
-          }
-          if (lane < 8 && j < sbs) {    // write L back (row j)
-#pragma unroll
-            for (int c = 0; c < 8; ++c)
-              if (c <= j) D[(size_t)(qb + j) * SA + qb + c] = row[c];
-          }
-          // trtri8: V column j by forward substitution; row i of L is
-          // gathered as rowi[c] = lane i's row[c]
-          float v[8];
-#pragma unroll
-          for (int i = 0; i < 8; ++i) v[i] = (i == j) ? myrs : 0.f;
-#pragma unroll
-          for (int i = 0; i < 8; ++i) {
-            float rowi[8];
-#pragma unroll
-            for (int c = 0; c < 8; ++c) rowi[c] = bcast_lane(row[c], i);
-            if (j < i) {
-              float sacc = 0.f;
+          for (int c = 0; c < 8; ++c) inv[c] *= myrs;   // V[j][c]; 0 for c > j
+          if (lane < 8) {
+            if (j < sbs) {              // write L back (row j)
 #pragma unroll
               for (int c = 0; c < 8; ++c)
-                if (c >= j && c < i) sacc += rowi[c] * v[c];
-              v[i] = -sacc * __builtin_amdgcn_rcpf(rowi[i]);
+                if (c <= j) D[(size_t)(qb + j) * SA + qb + c] = row[c];
             }
-          }
-          if (lane < 8) {
-#pragma unroll
-            for (int i = 0; i < 8; ++i) Vq[q * 64 + i * 8 + j] = v[i];
+            float* vo = Vq + q * 64 + j * 8;     // row j of V, contiguous
+            *(float4*)vo = make_float4(inv[0], inv[1], inv[2], inv[3]);
+            *(float4*)(vo + 4) = make_float4(inv[4], inv[5], inv[6], inv[7]);
           }
           // ok is the same in every lane (every pivot is a broadcast);
           // the exit decision is taken on lane 0's copy in an SGPR
@@ -381,8 +493,16 @@ __device__ inline void chol_invert_lower(float* Abuf, float* Tbuf,
           wave_lds_sync();           // next sub-block's inputs visible
         }
       }
+      unsigned long long jt2 = 0;
+      if (jclk && tid == 0) {
+        jt2 = wall_clock64();
+        jclk[2] += jt2 - jt1;
+      }
+      // the 32x32 inverse straight behind the q-loop, whose last
+      // wave_lds_sync() has made L and Vq visible to this wave
+      if (w0ok) assemble_diag_inverse(D, SA, Vq, bs, nq, lane);
       __builtin_amdgcn_s_setprio(0);
-      if (jclk && tid == 0) jclk[2] += wall_clock64() - jt1;
+      if (jclk && tid == 0) jclk[6] += wall_clock64() - jt2;
     } else if (J > 0) {
       // waves 1-7, one pass: previous panel's update to (a) the panel
       // rows of column-block J and (b) the remaining trailing triangle
@@ -403,53 +523,10 @@ __device__ inline void chol_invert_lower(float* Abuf, float* Tbuf,
       }
       if (jclk && tid == 64) jclk[3] += wall_clock64() - jt1;
     }
-    // the q-loop's one barrier: every wave arrives here whatever happened
-    // above (no workgroup barrier and no return inside either branch)
+    // phase 2's one barrier: every wave arrives here whatever happened
+    // above (no workgroup barrier and no return inside either branch); it
+    // publishes the assembled inverse of the diagonal block
     __syncthreads();
-    if (*bad == 0) {                 // uniform: read after the barrier
-      // ---- assemble V_JJ (32x32 inverse) from the 8x8 inverses --------
-      // column-blocks Jq descending; all target blocks of a column in
-      // parallel through TS; ALL threads
-      for (int Jq = nq - 1; Jq >= 0; --Jq) {
-        const int jb8 = Jq * 8;
-        const int nblks = nq - 1 - Jq;       // target blocks below
-        for (int f = tid; f < nblks * 64; f += WG) {
-          const int blk = f >> 6;            // 0..nblks-1
-          const int ib = (Jq + 1 + blk) * 8;
-          const int i = (f >> 3) & 7, j = f & 7;
-          const int gi = ib + i;
-          float u = 0.f;
-          if (gi < bs && jb8 + j < bs) {
-            // u = sum_{c=jb8+8}^{gi} V[gi][c] * L[c][jb8+j]
-            u = dotm(D + (size_t)gi * SA, D + jb8 + j, SA,
-                     jb8 + 8, min(gi + 1, bs));
-          }
-          TS[f] = u;
-        }
-        __syncthreads();
-        for (int f = tid; f < nblks * 64; f += WG) {
-          const int blk = f >> 6;
-          const int ib = (Jq + 1 + blk) * 8;
-          const int i = (f >> 3) & 7, j = f & 7;
-          const int gi = ib + i;
-          if (gi >= bs || jb8 + j >= bs) continue;
-          float sacc = 0.f;
-          const float* ts = TS + blk * 64 + i * 8;
-          const float* vv = Vq + Jq * 64;
-#pragma unroll
-          for (int t = 0; t < 8; ++t) sacc += ts[t] * vv[t * 8 + j];
-          D[(size_t)gi * SA + jb8 + j] = -sacc;
-        }
-        // this column's diagonal block <- its inverse (consumed as V by
-        // the shells of columns further left)
-        for (int f = tid; f < 64; f += WG) {
-          const int i = (f >> 3) & 7, j = f & 7;
-          const int gi = jb8 + i, gj = jb8 + j;
-          if (gi < bs && gj <= gi) D[(size_t)gi * SA + gj] = Vq[Jq * 64 + f];
-        }
-        __syncthreads();             // the last one ends the block
-      }
-    }
     if (jclk && tid == 0) {
       const unsigned long long t2 = wall_clock64();
       jclk[0] += jt1 - jt0;
