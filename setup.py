@@ -21,6 +21,8 @@ ext = CUDAExtension(
     sources=[
         "spark_gp_amd/ops/csrc/bindings.cpp",
         "spark_gp_amd/ops/csrc/expert_nll.hip",
+        "spark_gp_amd/ops/csrc/expert_nll_m32.hip",
+        "spark_gp_amd/ops/csrc/expert_nll_m52.hip",
         "spark_gp_amd/ops/csrc/cross_syrk.hip",
         "spark_gp_amd/ops/csrc/laplace.hip",
         "spark_gp_amd/ops/csrc/big_chol.hip",

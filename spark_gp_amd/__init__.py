@@ -20,9 +20,9 @@ Quick start::
 
 from .active_set import (ActiveSetProvider, GreedilyOptimizingActiveSetProvider,
                          KMeansActiveSetProvider, RandomActiveSetProvider)
-from .kernels import (ARDRBFKernel, EyeKernel, Kernel, Matern32Kernel,
-                      Matern52Kernel, RBFKernel, Scalar, SumOfKernels,
-                      WhiteNoiseKernel)
+from .kernels import (ARDMatern32Kernel, ARDMatern52Kernel, ARDRBFKernel,
+                      EyeKernel, Kernel, Matern32Kernel, Matern52Kernel,
+                      RBFKernel, Scalar, SumOfKernels, WhiteNoiseKernel)
 from .likelihoods import (Likelihood, LogisticLikelihood,
                           PoissonLikelihood, ProbitLikelihood)
 from .models import (GaussianProcessClassificationModel,
@@ -45,7 +45,8 @@ __all__ = [
     "Likelihood", "LogisticLikelihood", "PoissonLikelihood",
     "ProbitLikelihood",
     "Kernel", "RBFKernel", "ARDRBFKernel", "Matern32Kernel",
-    "Matern52Kernel", "EyeKernel", "WhiteNoiseKernel",
+    "Matern52Kernel", "ARDMatern32Kernel", "ARDMatern52Kernel",
+    "EyeKernel", "WhiteNoiseKernel",
     "SumOfKernels", "Scalar",
     "ActiveSetProvider", "RandomActiveSetProvider", "KMeansActiveSetProvider",
     "GreedilyOptimizingActiveSetProvider",

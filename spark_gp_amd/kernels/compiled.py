@@ -8,26 +8,84 @@ to
 
     K(theta) = C * Kb(theta_base)  +  nu(theta) * I
 
-with Kb a single stationary base (RBF or ARD-RBF), C either a constant or one
-trainable hyper, and nu = const + sum of trainable white-noise hypers.  The
+with Kb a single stationary base, C either a constant or one trainable hyper,
+and nu = const + sum of trainable white-noise hypers.  Six bases are
+recognised, each a function of q = ||(a - b) o s||^2 in coordinates scaled
+per dimension by s:
+
+    base       class               family       s_j
+    'rbf'      RBFKernel           exp(-q)      1 / (sqrt(2) sigma)
+    'ard'      ARDRBFKernel        exp(-q)      beta_j
+    'm32'      Matern32Kernel      Matérn 3/2   sqrt(3) / l
+    'ard_m32'  ARDMatern32Kernel   Matérn 3/2   sqrt(3) beta_j
+    'm52'      Matern52Kernel      Matérn 5/2   sqrt(5) / l
+    'ard_m52'  ARDMatern52Kernel   Matérn 5/2   sqrt(5) beta_j
+
+(``base_family``, ``base_nup``, ``base_is_ard`` and ``base_scale`` below; the
+family functions Kb(q) and Kd(q) = -dKb/dq are in ``kernels/matern.py``.)  The
 fused objective (torch batched or the hand-written HIP kernel) consumes this
 ``CompiledKernel`` and computes the per-expert negative log marginal
 likelihood *and its full gradient* without ever materializing the
 ``[p, k, k]`` derivative tensor the reference builds per expert
 (``kernel/ARDRBFKernel.scala:61-79``).
 
-Trees that do not match the pattern fall back to the generic batched path
+Trees that do not match the pattern (two stationary bases in one tree, nested
+trainable scalars, ...) fall back to the generic batched path
 (materialized derivatives) — full API generality is preserved.
 """
 
 from __future__ import annotations
 
+import math
 from dataclasses import dataclass, field
 from typing import List, Optional
 
+import numpy as np
+
 from .base import (ConstantTimesKernel, EyeKernel, Kernel, SumOfKernels,
                    TrainableScalarTimesKernel)
+from .matern import (ARDMatern32Kernel, ARDMatern52Kernel, Matern32Kernel,
+                     Matern52Kernel)
 from .rbf import ARDRBFKernel, RBFKernel
+
+# covariance family codes, as in ops/csrc/kernel_geom.h (GEOM_FAM_*)
+FAM_RBF, FAM_M32, FAM_M52 = 0, 1, 2
+
+# base string of each recognised class, and per base: (family code, nu', ARD)
+_BASE_OF = {RBFKernel: 'rbf', ARDRBFKernel: 'ard',
+            Matern32Kernel: 'm32', Matern52Kernel: 'm52',
+            ARDMatern32Kernel: 'ard_m32', ARDMatern52Kernel: 'ard_m52'}
+_BASE_INFO = {'rbf': (FAM_RBF, None, False), 'ard': (FAM_RBF, None, True),
+              'm32': (FAM_M32, 3.0, False), 'ard_m32': (FAM_M32, 3.0, True),
+              'm52': (FAM_M52, 5.0, False), 'ard_m52': (FAM_M52, 5.0, True)}
+BASES = tuple(_BASE_INFO)
+RBF_BASES = ('ard', 'rbf')
+
+
+def base_family(base: str) -> int:
+    """Family code the HIP kernels are instantiated for."""
+    return _BASE_INFO[base][0]
+
+
+def base_nup(base: str) -> Optional[float]:
+    """nu' of a Matérn base (3 or 5: q = nu' r^2 / l^2); None for RBF."""
+    return _BASE_INFO[base][1]
+
+
+def base_is_ard(base: str) -> bool:
+    """One scale hyper per input dimension (else a single length hyper)."""
+    return _BASE_INFO[base][2]
+
+
+def base_scale(base: str, theta_base, d: int) -> np.ndarray:
+    """The [d] coordinate scale s of the table above, in fp64."""
+    nup = base_nup(base)
+    if base_is_ard(base):
+        s = np.asarray(theta_base, dtype=np.float64)
+        return s if nup is None else math.sqrt(nup) * s
+    length = float(theta_base[0])
+    return np.full(d, 1.0 / (math.sqrt(2.0) * length) if nup is None
+                   else math.sqrt(nup) / length)
 
 
 @dataclass
@@ -39,7 +97,7 @@ class CompiledKernel:
     prepends)."""
 
     p: int                               # total number of hyperparameters
-    base: str                            # 'rbf' | 'ard' | 'none'
+    base: str                            # one of BASES
     base_idx: slice                      # slice of theta for the base kernel
     amp_idx: Optional[int]               # index of trainable amplitude C, or None
     amp_const: float                     # amplitude when amp_idx is None
@@ -55,7 +113,7 @@ class CompiledKernel:
 
 class _Acc:
     def __init__(self):
-        self.base = None          # ('rbf'|'ard', base_idx_slice, amp_idx, amp_const)
+        self.base = None          # (base, base_idx_slice, amp_idx, amp_const)
         self.noise_const = 0.0
         self.noise_idx: List[int] = []
         self.ok = True
@@ -88,11 +146,12 @@ def _walk(k: Kernel, offset: int, scale_const: float,
         else:
             acc.noise_const += scale_const
         return 0
-    if isinstance(k, (RBFKernel, ARDRBFKernel)):
+    kind = next((b for cls, b in _BASE_OF.items() if isinstance(k, cls)),
+                None)
+    if kind is not None:
         if acc.base is not None:
             acc.ok = False          # two stationary bases: fall back
             return k.num_hyperparameters
-        kind = 'rbf' if isinstance(k, RBFKernel) else 'ard'
         p = k.num_hyperparameters
         acc.base = (kind, slice(offset, offset + p), scale_idx,
                     scale_const if scale_idx is None else 1.0)

@@ -3,17 +3,33 @@ ships only the RBF family, ``kernel/RBFKernel.scala`` /
 ``kernel/ARDRBFKernel.scala``; Matérn 3/2 and 5/2 are the standard
 rough-process complements, Rasmussen & Williams ch. 4.2).
 
-Both take one trainable lengthscale ``l``:
+Isotropic, one trainable lengthscale ``l``:
 
 * ``Matern32Kernel`` — k(r) = (1 + s) exp(-s),            s = sqrt(3) r / l,
   dk/dl = s^2 exp(-s) / l.
 * ``Matern52Kernel`` — k(r) = (1 + s + s^2/3) exp(-s),    s = sqrt(5) r / l,
   dk/dl = s^2 (1 + s) exp(-s) / (3 l).
 
-They plug into the same DSL (`+`, scalar `*`, ``TrainableScalar``) and run
-through the generic objective path (``ops.nll_grad_generic``); there is no
-fused HIP fast path for them (the canonicalizer in ``kernels/compiled.py``
-recognizes the RBF family only).
+ARD, one trainable inverse lengthscale ``beta_j`` per input dimension, with
+``ARDRBFKernel``'s constructors, bounds and hyperparameter layout:
+
+* ``ARDMatern32Kernel`` / ``ARDMatern52Kernel`` — the same k(s) at
+  s = sqrt(nu' ||(a - b) o beta||^2), nu' = 3 resp. 5.
+
+All four share one form in the scaled squared distance q = s^2 (t = sqrt q):
+
+    Kb(q) = (1 + t) e^-t            Kd(q) := -dKb/dq = e^-t / 2          (3/2)
+    Kb(q) = (1 + t + t^2/3) e^-t    Kd(q) = (1 + t) e^-t / 6             (5/2)
+
+so dk/dbeta_j = -2 nu' Kd beta_j (a_j - b_j)^2, with no singularity at t = 0.
+
+They plug into the same DSL (`+`, scalar `*`, ``TrainableScalar``).  A tree
+``C * Matern + noise`` canonicalizes (``kernels/compiled.py``) and trains on
+the fused objective — the hand-written HIP kernels on a GPU, instantiated per
+family — and predicts through the HIP cross kernel and PPA accumulation.
+Other trees (two stationary bases, say) run the generic path through the
+materialized derivatives below.  The fused Laplace kernels stay RBF-only: a
+Matérn classifier runs the torch Laplace path.
 """
 
 from __future__ import annotations
@@ -25,6 +41,7 @@ import numpy as np
 import torch
 
 from .base import Kernel, sqdist, _as_f64
+from .rbf import ARDRBFKernel
 
 _EPS = 1e-30  # guards r=0 in d/dl (the derivative -> 0 there anyway)
 
@@ -108,3 +125,65 @@ class Matern52Kernel(_MaternBase):
 
     def __repr__(self):
         return f"Matern52Kernel(l={self.l:.1e})"
+
+
+class _ARDMaternBase(Kernel):
+    """k = Kb(nu' ||(a - b) o beta||^2); constructors, bounds and layout are
+    ``ARDRBFKernel``'s."""
+
+    NUP = 0.0                     # nu': 3 (Matérn 3/2) or 5 (Matérn 5/2)
+
+    __init__ = ARDRBFKernel.__init__
+    get_hyperparameters = ARDRBFKernel.get_hyperparameters
+    set_hyperparameters = ARDRBFKernel.set_hyperparameters
+    num_hyperparameters = ARDRBFKernel.num_hyperparameters
+    hyperparameter_bounds = ARDRBFKernel.hyperparameter_bounds
+    white_noise_var = ARDRBFKernel.white_noise_var
+    training_kernel_diag = ARDRBFKernel.training_kernel_diag
+    self_kernel = ARDRBFKernel.self_kernel
+    _beta_t = ARDRBFKernel._beta_t
+
+    @staticmethod
+    def _kb_kd(t):
+        """(Kb, Kd) at t = sqrt(q)."""
+        raise NotImplementedError
+
+    def _t(self, A, B):
+        s = self._beta_t(B) * math.sqrt(self.NUP)
+        return torch.sqrt(sqdist(A * s, B * s).clamp_min(0.0))
+
+    def training_kernel(self, X):
+        return self._kb_kd(self._t(X, X))[0]
+
+    def training_kernel_and_derivative(self, X):
+        K, Kd = self._kb_kd(self._t(X, X))
+        beta = self._beta_t(X)
+        diff = X.unsqueeze(-2) - X.unsqueeze(-3)          # [..., n, n, d]
+        dK = (-2.0 * self.NUP * beta) * (diff * diff)     # [..., n, n, d]
+        dK = dK.permute(*range(dK.dim() - 3), -1, -3, -2) # [..., d, n, n]
+        return K, dK * Kd.unsqueeze(-3)
+
+    def cross_kernel(self, Xtest, Xtrain):
+        return self._kb_kd(self._t(Xtest, Xtrain))[0]
+
+    def __repr__(self):
+        vals = ", ".join(f"{b:.1e}" for b in self.beta)
+        return f"{type(self).__name__}(beta=[{vals}])"
+
+
+class ARDMatern32Kernel(_ARDMaternBase):
+    NUP = 3.0
+
+    @staticmethod
+    def _kb_kd(t):
+        e = torch.exp(-t)
+        return (1.0 + t) * e, 0.5 * e
+
+
+class ARDMatern52Kernel(_ARDMaternBase):
+    NUP = 5.0
+
+    @staticmethod
+    def _kb_kd(t):
+        e = torch.exp(-t)
+        return (1.0 + t + t * t / 3.0) * e, (1.0 + t) * e / 6.0

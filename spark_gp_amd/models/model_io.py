@@ -16,8 +16,9 @@ from typing import Dict
 
 import numpy as np
 
-from ..kernels import (ARDRBFKernel, ConstantTimesKernel, EyeKernel, Kernel,
-                       Matern32Kernel, Matern52Kernel, RBFKernel, SumOfKernels,
+from ..kernels import (ARDMatern32Kernel, ARDMatern52Kernel, ARDRBFKernel,
+                       ConstantTimesKernel, EyeKernel, Kernel, Matern32Kernel,
+                       Matern52Kernel, RBFKernel, SumOfKernels,
                        TrainableScalarTimesKernel)
 from .classification import GaussianProcessClassificationModel
 from .poisson import GaussianProcessPoissonModel
@@ -40,6 +41,11 @@ def _dec(x):
     return x
 
 
+# spec op of each ARD class (one beta per input dimension, same fields)
+_ARD_OPS = {ARDRBFKernel: "ard", ARDMatern32Kernel: "ard_m32",
+            ARDMatern52Kernel: "ard_m52"}
+
+
 def kernel_to_spec(k: Kernel) -> Dict:
     if isinstance(k, SumOfKernels):
         return {"op": "sum", "args": [kernel_to_spec(k.k1), kernel_to_spec(k.k2)]}
@@ -56,8 +62,8 @@ def kernel_to_spec(k: Kernel) -> Dict:
     if isinstance(k, (Matern32Kernel, Matern52Kernel)):
         return {"op": "m32" if isinstance(k, Matern32Kernel) else "m52",
                 "l": k.l, "lower": _enc(k.lower), "upper": _enc(k.upper)}
-    if isinstance(k, ARDRBFKernel):
-        return {"op": "ard", "beta": k.beta.tolist(),
+    if isinstance(k, (ARDRBFKernel, ARDMatern32Kernel, ARDMatern52Kernel)):
+        return {"op": _ARD_OPS[type(k)], "beta": k.beta.tolist(),
                 "lower": [_enc(float(v)) for v in k.lower],
                 "upper": [_enc(float(v)) for v in k.upper]}
     raise TypeError(f"cannot serialize kernel type {type(k).__name__}")
@@ -81,11 +87,11 @@ def kernel_from_spec(spec: Dict) -> Kernel:
     if op in ("m32", "m52"):
         cls = Matern32Kernel if op == "m32" else Matern52Kernel
         return cls(spec["l"], _dec(spec["lower"]), _dec(spec["upper"]))
-    if op == "ard":
-        return ARDRBFKernel(np.array(spec["beta"]),
-                            beta=1.0,
-                            lower=np.array([_dec(v) for v in spec["lower"]]),
-                            upper=np.array([_dec(v) for v in spec["upper"]]))
+    if op in _ARD_OPS.values():
+        cls = next(c for c, o in _ARD_OPS.items() if o == op)
+        return cls(np.array(spec["beta"]), beta=1.0,
+                   lower=np.array([_dec(v) for v in spec["lower"]]),
+                   upper=np.array([_dec(v) for v in spec["upper"]]))
     raise ValueError(f"unknown kernel spec op {op!r}")
 
 

@@ -19,7 +19,7 @@ import numpy as np
 import torch
 
 from ..kernels.base import Kernel
-from ..kernels.compiled import CompiledKernel
+from ..kernels.compiled import BASES, CompiledKernel
 from . import torch_backend
 
 _hip = None
@@ -69,7 +69,7 @@ def nll_grad_compiled(cs: CompiledKernel, theta: np.ndarray,
                       X: torch.Tensor, y: torch.Tensor
                       ) -> Tuple[float, np.ndarray]:
     hip = (_backend_for("nll_grad_compiled", X)
-           if cs.base in ("ard", "rbf") else None)
+           if cs.base in BASES else None)
     if hip is not None and hip.supports_nll(cs, X):
         return hip.nll_grad_compiled(cs, theta, X, y)
     return torch_backend.nll_grad_compiled(cs, theta, X, y)

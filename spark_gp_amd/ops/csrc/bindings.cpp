@@ -85,6 +85,12 @@ void make_contiguous(std::initializer_list<torch::Tensor*> ts) {
   for (torch::Tensor* t : ts) *t = t->contiguous();
 }
 
+// the covariance family code of an entry point (kernel_geom.h)
+void check_family(int64_t family) {
+  TORCH_CHECK(geom_family_ok(family), "family must be 0 (RBF), 1 (Matern "
+              "3/2) or 2 (Matern 5/2), got ", family);
+}
+
 torch::TensorOptions like(const torch::Tensor& t, torch::ScalarType dtype) {
   return torch::TensorOptions().dtype(dtype).device(t.device());
 }
@@ -96,7 +102,9 @@ std::vector<torch::Tensor> fused_expert_nll_impl(torch::Tensor X,
                                                  torch::Tensor y,
                                                  torch::Tensor scale,
                                                  double amp, double noise,
-                                                 bool profile) {
+                                                 bool profile,
+                                                 int64_t family) {
+  check_family(family);
   check_arg(X, "X", F32, {ANY, ANY, ANY});
   const int E = X.size(0), k = X.size(1), d = X.size(2);
   check_arg(y, "y", F32, {E, k});
@@ -120,7 +128,7 @@ std::vector<torch::Tensor> fused_expert_nll_impl(torch::Tensor X,
                 scale.data_ptr<float>(), (float)amp, (float)noise, E, k, d,
                 nll.data_ptr<double>(), sumW0.data_ptr<double>(),
                 trG.data_ptr<double>(), contr.data_ptr<double>(),
-                bad.data_ptr<int>(), clk_ptr, current_stream()),
+                bad.data_ptr<int>(), clk_ptr, (int)family, current_stream()),
             "fused_expert_nll");
   if (profile) return {nll, sumW0, trG, contr, bad, clk};
   return {nll, sumW0, trG, contr, bad};
@@ -128,8 +136,8 @@ std::vector<torch::Tensor> fused_expert_nll_impl(torch::Tensor X,
 
 std::vector<torch::Tensor> fused_expert_nll(torch::Tensor X, torch::Tensor y,
                                             torch::Tensor scale, double amp,
-                                            double noise) {
-  return fused_expert_nll_impl(X, y, scale, amp, noise, false);
+                                            double noise, int64_t family) {
+  return fused_expert_nll_impl(X, y, scale, amp, noise, false, family);
 }
 
 bool fused_expert_nll_supported(int64_t k, int64_t d) {
@@ -137,19 +145,21 @@ bool fused_expert_nll_supported(int64_t k, int64_t d) {
   return nll_lds_bytes((int)k, (int)d) <= GEOM_LDS_MAX;
 }
 
-// Workgroups of fused_expert_nll_kernel the HIP runtime reports resident per
+// Workgroups of the family's fused_expert_nll kernel the HIP runtime reports resident per
 // CU (hipOccupancyMaxActiveBlocksPerMultiprocessor) at the launch's real
 // block size and dynamic LDS, on the current device.
-int64_t fused_expert_nll_occupancy(int64_t k, int64_t d) {
+int64_t fused_expert_nll_occupancy(int64_t k, int64_t d, int64_t family) {
+  check_family(family);
   TORCH_CHECK(k >= 1 && k <= 128, "k must be in [1, 128], got ", k);
   TORCH_CHECK(d >= 1 && d <= 128, "d must be in [1, 128], got ", d);
   int wgs = 0;
-  check_hip(fused_expert_nll_resident_wgs((int)k, (int)d, &wgs),
+  check_hip(fused_expert_nll_resident_wgs((int)k, (int)d, (int)family, &wgs),
             "fused_expert_nll_occupancy");
   return wgs;
 }
 
-// The elementwise RBF/ARD tile in both of its uses.  want_cm: write the
+// The elementwise tile (q by differences, then the family's Kb) in both of
+// its uses.  want_cm: write the
 // [c, m] copies (hi, and lo with hilo); want_t: write the transposed hi/lo
 // pair; y/Ky (both or neither): also accumulate Ky += K^T y from the fp32
 // register values.  Returns the tensors written, in the order
@@ -157,7 +167,8 @@ int64_t fused_expert_nll_occupancy(int64_t k, int64_t d) {
 static std::vector<torch::Tensor> cross_tile(
     const char* what, torch::Tensor X, torch::Tensor A, torch::Tensor s2v,
     double amp, bool bf16_out, bool want_cm, bool hilo, bool want_t,
-    torch::Tensor* y, const torch::Tensor* Ky) {
+    torch::Tensor* y, const torch::Tensor* Ky, int64_t family) {
+  check_family(family);
   check_arg(X, "X", F32, {ANY, ANY});
   const int c = X.size(0), d = X.size(1);
   check_arg(A, "A", F32, {ANY, d});
@@ -184,7 +195,8 @@ static std::vector<torch::Tensor> cross_tile(
                 ptr_or_null(lo), ptr_or_null(outT), ptr_or_null(loT),
                 bf16_out ? 1 : 0,
                 y ? y->data_ptr<float>() : nullptr,
-                y ? Ky->data_ptr<double>() : nullptr, current_stream()),
+                y ? Ky->data_ptr<double>() : nullptr, (int)family,
+                current_stream()),
             what);
   std::vector<torch::Tensor> res;
   for (const auto& t : {out, lo, outT, loT})
@@ -195,11 +207,11 @@ static std::vector<torch::Tensor> cross_tile(
 std::vector<torch::Tensor> cross_kernel_tile(torch::Tensor X, torch::Tensor A,
                                              torch::Tensor s2v, double amp,
                                              bool bf16_out, bool hilo,
-                                             bool want_t) {
+                                             bool want_t, int64_t family) {
   TORCH_CHECK(!hilo || bf16_out, "hilo requires bf16 output");
   TORCH_CHECK(!want_t || hilo, "transposed outputs require hilo bf16 mode");
   return cross_tile("cross_kernel_tile", X, A, s2v, amp, bf16_out, true, hilo,
-                    want_t, nullptr, nullptr);
+                    want_t, nullptr, nullptr, family);
 }
 
 // PPA fast path: transposed hi/lo tiles ONLY (no [c, m] copies written)
@@ -209,9 +221,10 @@ std::vector<torch::Tensor> cross_kernel_tile_ppa(torch::Tensor X,
                                                  torch::Tensor A,
                                                  torch::Tensor s2v,
                                                  double amp, torch::Tensor y,
-                                                 torch::Tensor Ky) {
+                                                 torch::Tensor Ky,
+                                                 int64_t family) {
   return cross_tile("cross_kernel_tile_ppa", X, A, s2v, amp, true, false,
-                    true, true, &y, &Ky);
+                    true, true, &y, &Ky, family);
 }
 
 // Shapes of the pre-scaled PPA inputs shared by cross_mfma_ppa and
@@ -231,7 +244,8 @@ static void check_ppa_inputs(const torch::Tensor& Xs, const torch::Tensor& As,
 std::vector<torch::Tensor> cross_mfma_ppa(torch::Tensor Xs, torch::Tensor As,
                                           torch::Tensor nx, torch::Tensor na,
                                           double amp, torch::Tensor y,
-                                          torch::Tensor Ky) {
+                                          torch::Tensor Ky, int64_t family) {
+  check_family(family);
   check_ppa_inputs(Xs, As, nx, na, y, Ky);
   check_same_gpu({{&Xs, "Xs"}, {&As, "As"}, {&nx, "nx"}, {&na, "na"},
                   {&y, "y"}, {&Ky, "Ky"}});
@@ -243,7 +257,8 @@ std::vector<torch::Tensor> cross_mfma_ppa(torch::Tensor Xs, torch::Tensor As,
                               nx.data_ptr<float>(), na.data_ptr<float>(),
                               (float)amp, c, m, d, outT.data_ptr(),
                               loT.data_ptr(), y.data_ptr<float>(),
-                              Ky.data_ptr<double>(), current_stream()),
+                              Ky.data_ptr<double>(), (int)family,
+                              current_stream()),
             "cross_mfma_ppa");
   return {outT, loT};
 }
@@ -313,7 +328,9 @@ bool ppa_fused_supported(int64_t m, int64_t d) {
 
 void ppa_fused_acc(torch::Tensor Xs, torch::Tensor As, torch::Tensor nx,
                    torch::Tensor na, double amp, torch::Tensor y,
-                   torch::Tensor Ky, torch::Tensor KK, int64_t split_k) {
+                   torch::Tensor Ky, torch::Tensor KK, int64_t split_k,
+                   int64_t family) {
+  check_family(family);
   check_ppa_inputs(Xs, As, nx, na, y, Ky);
   const int c = Xs.size(0), m = As.size(0), d = Xs.size(1);
   TORCH_CHECK(ppa_fused_supported(m, d), "As: unsupported (m, d) for "
@@ -329,7 +346,7 @@ void ppa_fused_acc(torch::Tensor Xs, torch::Tensor As, torch::Tensor nx,
                 Xs.data_ptr<float>(), As.data_ptr<float>(),
                 nx.data_ptr<float>(), na.data_ptr<float>(), (float)amp,
                 y.data_ptr<float>(), c, m, d, (int)split_k,
-                Ky.data_ptr<double>(), KK.data_ptr<float>(),
+                Ky.data_ptr<double>(), KK.data_ptr<float>(), (int)family,
                 current_stream()),
             "ppa_fused_acc");
 }
@@ -528,6 +545,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.attr("SY_BK") = (int)SY_BK;
   mod.attr("SF_DMAX") = (int)SF_DMAX;
   mod.attr("SY_SPLITK_MAX_TILES") = (int)SY_SPLITK_MAX_TILES;
+  // covariance family codes of the `family` arguments below
+  mod.attr("FAM_RBF") = (int)GEOM_FAM_RBF;
+  mod.attr("FAM_M32") = (int)GEOM_FAM_M32;
+  mod.attr("FAM_M52") = (int)GEOM_FAM_M52;
   mod.def("synth_regression", &synth_regression,
           "device-side Philox benchmark data (K19)");
   mod.def("dpotrf64", &dpotrf64,
@@ -545,24 +566,37 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("fused_laplace_evidence_supported",
           &fused_laplace_evidence_supported);
   mod.def("fused_expert_nll", &fused_expert_nll,
-          "fused per-expert BCM nll+gradient primitives (CDNA4)");
+          "fused per-expert BCM nll+gradient primitives (CDNA4)",
+          pybind11::arg("X"), pybind11::arg("y"), pybind11::arg("scale"), pybind11::arg("amp"), pybind11::arg("noise"),
+          pybind11::arg("family") = (int)GEOM_FAM_RBF);
   mod.def("fused_expert_nll_profile", &fused_expert_nll_impl,
-          "same, with per-phase wall_clock64 boundaries appended");
+          "same, with per-phase wall_clock64 boundaries appended",
+          pybind11::arg("X"), pybind11::arg("y"), pybind11::arg("scale"), pybind11::arg("amp"), pybind11::arg("noise"),
+          pybind11::arg("profile"), pybind11::arg("family") = (int)GEOM_FAM_RBF);
   mod.def("fused_expert_nll_supported", &fused_expert_nll_supported);
   mod.def("fused_expert_nll_occupancy", &fused_expert_nll_occupancy,
-          "resident workgroups per CU of the expert kernel at (k, d)");
+          "resident workgroups per CU of the expert kernel at (k, d)",
+          pybind11::arg("k"), pybind11::arg("d"), pybind11::arg("family") = (int)GEOM_FAM_RBF);
   mod.def("cross_mfma_ppa", &cross_mfma_ppa,
-          "MFMA sqdist cross tile + fused K^T y (K1 plan, CDNA4)");
+          "MFMA sqdist cross tile + fused K^T y (K1 plan, CDNA4)",
+          pybind11::arg("Xs"), pybind11::arg("As"), pybind11::arg("nx"), pybind11::arg("na"), pybind11::arg("amp"), pybind11::arg("y"),
+          pybind11::arg("Ky"), pybind11::arg("family") = (int)GEOM_FAM_RBF);
   mod.def("ppa_fused_acc", &ppa_fused_acc,
-          "KK += K^T K, Ky += K^T y with K_nm generated in the SYRK (CDNA4)");
+          "KK += K^T K, Ky += K^T y with K_nm generated in the SYRK (CDNA4)",
+          pybind11::arg("Xs"), pybind11::arg("As"), pybind11::arg("nx"), pybind11::arg("na"), pybind11::arg("amp"), pybind11::arg("y"),
+          pybind11::arg("Ky"), pybind11::arg("KK"), pybind11::arg("split_k"),
+          pybind11::arg("family") = (int)GEOM_FAM_RBF);
   mod.def("ppa_fused_supported", &ppa_fused_supported);
   mod.def("cross_kernel_tile_ppa", &cross_kernel_tile_ppa,
-          "transposed hi/lo tiles + fused K^T y accumulation (CDNA4)");
+          "transposed hi/lo tiles + fused K^T y accumulation (CDNA4)",
+          pybind11::arg("X"), pybind11::arg("A"), pybind11::arg("s2v"), pybind11::arg("amp"), pybind11::arg("y"), pybind11::arg("Ky"),
+          pybind11::arg("family") = (int)GEOM_FAM_RBF);
   mod.def("cross_kernel_tile", &cross_kernel_tile,
-          "rectangular RBF/ARD kernel block (CDNA4)",
+          "rectangular kernel block of a covariance family (CDNA4)",
           pybind11::arg("X"), pybind11::arg("A"), pybind11::arg("s2v"),
           pybind11::arg("amp"), pybind11::arg("bf16_out"),
-          pybind11::arg("hilo"), pybind11::arg("want_t") = false);
+          pybind11::arg("hilo"), pybind11::arg("want_t") = false,
+          pybind11::arg("family") = (int)GEOM_FAM_RBF);
   mod.def("syrk_bf16_sync_acc", &syrk_bf16_sync_acc,
           "k-synchronized persistent SYRK for large m (CDNA4)");
   mod.def("syrk_bf16_acc", &syrk_bf16_acc,

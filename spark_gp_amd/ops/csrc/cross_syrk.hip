@@ -1,6 +1,6 @@
 // PPA accumulation kernels for MI355X (gfx950, CDNA4):
 //
-//  * cross_kernel_tile  — K_nm[c, m] = amp * exp(-sum_d s2_d (x - a)^2),
+//  * cross_kernel_tile  — K_nm[c, m] = amp * Kb(q), q = sum_d s2_d (x - a)^2,
 //    the rectangular kernel block (K6 in SURVEY.md §2.4), bf16 or fp32 out.
 //  * syrk_bf16          — KK[m, m] += K_nm^T K_nm over a chunk (K12, the
 //    rows/sec-dominating GEMM): MFMA bf16 16x16x32 tiles, LDS-staged with
@@ -29,6 +29,13 @@
 // split (split_hilo) are shared by the kernel that stores K_nm and the one
 // that generates it.  Tile constants shared with the host: kernel_geom.h.
 //
+// The three kernels that evaluate the covariance function (cross_kernel_tile,
+// cross_mfma, syrk_fused_gen) are templates over the family code of
+// kernel_geom.h (RBF: Kb = exp(-q); Matern 3/2 and 5/2 over t = sqrt(q)) and
+// are instantiated for each; nothing else here depends on the family.  The
+// RBF instances are instruction for instruction the kernels they were before
+// the template parameter.
+//
 // Replaces ProjectedGaussianProcessHelper.scala:20-36's per-expert
 // crossKernel + breeze gemm accumulation.
 
@@ -44,12 +51,14 @@ typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 
 // K_nm from pre-scaled inputs: q = ||x'||^2 + ||a'||^2 - 2 x'.a' clamped at
-// 0, v = amp exp(-q).  cross_mfma_kernel stores these values and
-// syrk_fused_gen_kernel generates them; both call this one definition.
+// 0, v = amp Kb(q) of the family (kernel_geom.h; RBF: amp exp(-q)).
+// cross_mfma_kernel stores these values and syrk_fused_gen_kernel generates
+// them; both call this one definition.
+template <int FAM>
 __device__ __forceinline__ float knm_value(const float nx, const float na,
                                            const float dot, const float amp) {
   const float q = nx + na - 2.0f * dot;
-  return amp * __expf(-(q > 0.f ? q : 0.f));
+  return amp * family_kb<FAM>(q);
 }
 
 // hi/lo split: hi + lo carries ~16 mantissa bits, so the SYRK's
@@ -67,7 +76,8 @@ __device__ __forceinline__ void split_hilo(const float v, bf16& hi, bf16& lo) {
 #define CK_TILE 128
 #define CK_DBLK 32
 
-extern "C" __global__ void __launch_bounds__(256)
+template <int FAM>
+__global__ void __launch_bounds__(256)
 cross_kernel_tile_kernel(const float* __restrict__ X,    // [c, d]
                          const float* __restrict__ A,    // [m, d]
                          const float* __restrict__ s2v,  // [d] scale^2
@@ -136,7 +146,9 @@ cross_kernel_tile_kernel(const float* __restrict__ X,    // [c, d]
   for (int i = 0; i < 8; ++i)
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-      const float v = amp * __expf(-acc[i][j]);
+      // acc is a sum of squares: no clamp
+      const float v = amp * (FAM == GEOM_FAM_RBF ? __expf(-acc[i][j])
+                                                 : family_kb<FAM>(acc[i][j]));
       acc[i][j] = v;
       split_hilo(v, hv[i][j], lv[i][j]);
     }
@@ -233,7 +245,8 @@ cross_kernel_tile_kernel(const float* __restrict__ X,    // [c, d]
 
 typedef __attribute__((ext_vector_type(4))) float f32x4_;
 
-extern "C" __global__ void __launch_bounds__(256)
+template <int FAM>
+__global__ void __launch_bounds__(256)
 cross_mfma_kernel(const float* __restrict__ Xs,   // [c, d] pre-scaled
                   const float* __restrict__ As,   // [m, d] pre-scaled
                   const float* __restrict__ nx,   // [c] ||x'||^2
@@ -320,7 +333,7 @@ cross_mfma_kernel(const float* __restrict__ Xs,   // [c, d] pre-scaled
         const int gr = gr0 + r;
         float v = 0.f;
         if (gr < c) {
-          v = knm_value(nx[gr], nav, acc[a][b][r], amp);
+          v = knm_value<FAM>(nx[gr], nav, acc[a][b][r], amp);
           kysum += v * yv[gr];
         }
         split_hilo(v, th[r], tl[r]);
@@ -691,7 +704,7 @@ syrk_bf16_kernel(const bf16* __restrict__ KcT,  // [m, cpitch] hi^T
                       // 36*l16 mod 64 is a permutation of 4-bank blocks, so
                       // the A-fragment reads (l16 rows x 4 k) are conflict-free
 
-template <bool DIAG>
+template <bool DIAG, int FAM>
 __device__ __forceinline__ void
 sf_tile(const float* __restrict__ Xs, const float* __restrict__ As,
         const float* __restrict__ nx, const float* __restrict__ na,
@@ -812,7 +825,7 @@ sf_tile(const float* __restrict__ Xs, const float* __restrict__ As,
         float kysum = 0.f;
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          float v = knm_value(nxr[r], nav[g], dacc[rg][g][r], amp);
+          float v = knm_value<FAM>(nxr[r], nav[g], dacc[rg][g][r], amp);
           v = (cok[g] && gr0 + r < c) ? v : 0.f;   // exact zeros outside
           if (DIAG) kysum += v * yr[r];            // y stages 0 for rows >= c
           split_hilo(v, th[r], tl[r]);
@@ -880,6 +893,7 @@ sf_tile(const float* __restrict__ Xs, const float* __restrict__ As,
   }
 }
 
+template <int FAM>
 __global__ void __launch_bounds__(SY_WG, 2)
 syrk_fused_gen_kernel(const float* __restrict__ Xs,   // [c, d] pre-scaled
                       const float* __restrict__ As,   // [m, d] pre-scaled
@@ -906,11 +920,13 @@ syrk_fused_gen_kernel(const float* __restrict__ Xs,   // [c, d] pre-scaled
   if (!syrk_kslice(c, split_k, blockIdx.y, kb0, kb1)) return;
 
   if (ti == tj)
-    sf_tile<true>(Xs, As, nx, na, amp, yv, c, m, d, ti * SY_CT, tj * SY_CT,
-                  kb0, kb1, lt, rt, ltl, rtl, xs, aw, Ky, KK);
+    sf_tile<true, FAM>(Xs, As, nx, na, amp, yv, c, m, d, ti * SY_CT,
+                       tj * SY_CT, kb0, kb1, lt, rt, ltl, rtl, xs, aw, Ky,
+                       KK);
   else
-    sf_tile<false>(Xs, As, nx, na, amp, yv, c, m, d, ti * SY_CT, tj * SY_CT,
-                   kb0, kb1, lt, rt, ltl, rtl, xs, aw, Ky, KK);
+    sf_tile<false, FAM>(Xs, As, nx, na, amp, yv, c, m, d, ti * SY_CT,
+                        tj * SY_CT, kb0, kb1, lt, rt, ltl, rtl, xs, aw, Ky,
+                        KK);
 }
 
 // ---------------------------------------------------------------------------
@@ -1010,13 +1026,22 @@ colsum_gemv_kernel(const bf16* __restrict__ Kc,   // [c, m]
 // ---------------------------------------------------------------------------
 // launchers
 // ---------------------------------------------------------------------------
+// KERNEL<family>, or null for an unknown family code
+#define FAMILY_KERNEL(KERNEL, family)                       \
+  ((family) == GEOM_FAM_RBF   ? KERNEL<GEOM_FAM_RBF>        \
+   : (family) == GEOM_FAM_M32 ? KERNEL<GEOM_FAM_M32>        \
+   : (family) == GEOM_FAM_M52 ? KERNEL<GEOM_FAM_M52>        \
+                              : nullptr)
+
 extern "C" hipError_t launch_cross_kernel_tile(
     const float* X, const float* A, const float* s2v, float amp,
     int c, int m, int d, void* out, void* out_lo, void* out_t,
     void* out_lo_t, int out_is_bf16, const float* yv, double* Ky,
-    hipStream_t stream) {
+    int family, hipStream_t stream) {
+  const auto kern = FAMILY_KERNEL(cross_kernel_tile_kernel, family);
+  if (!kern) return hipErrorInvalidValue;
   dim3 grid((c + CK_TILE - 1) / CK_TILE, (m + CK_TILE - 1) / CK_TILE);
-  hipLaunchKernelGGL(cross_kernel_tile_kernel, grid, dim3(256), 0, stream,
+  hipLaunchKernelGGL(kern, grid, dim3(256), 0, stream,
                      X, A, s2v, amp, c, m, d,
                      out_is_bf16 ? (bf16*)out : nullptr,
                      out_is_bf16 ? (bf16*)out_lo : nullptr,
@@ -1030,9 +1055,11 @@ extern "C" hipError_t launch_cross_mfma(const float* Xs, const float* As,
                                          float amp, int c, int m, int d,
                                          void* out_bfT, void* out_loT,
                                          const float* yv, double* Ky,
-                                         hipStream_t stream) {
+                                         int family, hipStream_t stream) {
+  const auto kern = FAMILY_KERNEL(cross_mfma_kernel, family);
+  if (!kern) return hipErrorInvalidValue;
   dim3 grid((c + CM_TILE - 1) / CM_TILE, (m + CM_TILE - 1) / CM_TILE);
-  hipLaunchKernelGGL(cross_mfma_kernel, grid, dim3(256), 0, stream,
+  hipLaunchKernelGGL(kern, grid, dim3(256), 0, stream,
                      Xs, As, nx, na, amp, c, m, d,
                      (bf16*)out_bfT, (bf16*)out_loT, yv, Ky);
   return hipGetLastError();
@@ -1076,10 +1103,12 @@ extern "C" hipError_t launch_syrk_bf16(const void* KcT, const void* KlT,
 extern "C" hipError_t launch_syrk_fused_gen(
     const float* Xs, const float* As, const float* nx, const float* na,
     float amp, const float* yv, int c, int m, int d, int split_k,
-    double* Ky, float* KK, hipStream_t stream) {
+    double* Ky, float* KK, int family, hipStream_t stream) {
+  const auto kern = FAMILY_KERNEL(syrk_fused_gen_kernel, family);
+  if (!kern) return hipErrorInvalidValue;
   const int ntile = (m + SY_CT - 1) / SY_CT;
   dim3 grid(ntile * (ntile + 1) / 2, split_k);   // upper-triangle tiles
-  hipLaunchKernelGGL(syrk_fused_gen_kernel, grid, dim3(SY_WG), 0, stream,
+  hipLaunchKernelGGL(kern, grid, dim3(SY_WG), 0, stream,
                      Xs, As, nx, na, amp, yv, c, m, d, ntile, split_k, Ky,
                      KK);
   return hipGetLastError();

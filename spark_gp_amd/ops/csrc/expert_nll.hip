@@ -9,7 +9,8 @@
 // between stages, and WITHOUT materializing the [d, k, k] derivative tensor:
 //
 //   B  lower(A) = amp*Kb + noise*I,  strict upper(A) = Kb (cached base
-//      kernel — read back in phase W, never recomputed); round 2: the
+//      kernel — read back in phase W, never recomputed; the Matern families
+//      cache t = sqrt(q) there instead, see below); round 2: the
 //      sqdist is q = n_a + n_b - 2 x'.a' over pre-SCALED coordinates on
 //      f32 MFMA tiles (the gradient contraction runs in scaled space and
 //      is de-scaled by s2 at output)
@@ -34,8 +35,9 @@
 //   E  alpha = V^T (V y);  nll = 1/2 y.alpha + 1/2 logdet
 //   L  lauum K^-1 = V^T V on f32 MFMA (masked fragments, register tiles
 //      across a barrier; strictly lower+diagonal so the Kb cache survives)
-//   W  W0 = (alpha alpha^T - K^-1) o Kb (Kb from the upper-triangle cache);
-//      trG / sum(W0) accumulated on the fly
+//   W  W0 = (alpha alpha^T - K^-1) o Kd, Kd = -dKb/dq (RBF: Kd = Kb, from
+//      the upper-triangle cache); trG and sumW0 = sum (alpha alpha^T -
+//      K^-1) o Kb accumulated on the fly
 //   H  gradient contraction per input dim (the K5 fusion)
 //      on f32 MFMA: W0 @ X' as 16x16x4 tiles, folded per fragment into
 //      per-column partials; contr de-scaled by s2 at output
@@ -50,6 +52,19 @@
 // global X) => 52 KB LDS at k=100, and at most 80 VGPRs at 6 waves/SIMD:
 // three experts resident per CU (profiles/PROFILES.md rounds 4 and 5;
 // fused_expert_nll_resident_wgs asks the runtime).
+//
+// Covariance families (kernel_geom.h): the kernel is compiled for exp(-q)
+// (RBF / ARD-RBF) and for Matern 3/2 and 5/2 over the same scaled q; only
+// the two epilogues of B and the products of W know the family.  With
+// G = alpha alpha^T - K^-1 the gradient needs sum(G o Kb) (amplitude) and
+// W = G o Kd (everything G and H contract); for RBF the two coincide.  The
+// Matern kernels cache t = sqrt(q) in the strict upper triangle, which is
+// exact and needs no LDS beyond the RBF plan's, and phase W forms Kb and Kd
+// from one exp(-t) per lower-triangle element (the diagonal takes t = 0:
+// Kb = 1, Kd = Kd(0), no 1/t anywhere).  Known edge: near-duplicate rows
+// make the GEMM-form q noisy at the 1e-6 ||x'||^2 level, and after the square
+// root Kd carries about 1e-3 relative error on those pairs only; Kb is
+// unaffected to first order.
 //
 // Numerics: fp32 storage/factorization, fp64 scalar accumulation.  Experts
 // whose fp32 Cholesky breaks down are flagged in out_bad and recomputed on
@@ -129,19 +144,34 @@ __device__ inline float scaled_sqnorm(const float* __restrict__ x,
 // tile pays one memory latency per XCH*4 contraction indices
 #define XCH 4
 
+// The kernel is compiled once per covariance family (kernel_geom.h), one
+// front per translation unit: this file by itself gives the RBF front,
+// fused_expert_nll_kernel, and the launchers; expert_nll_m32.hip and
+// expert_nll_m52.hip define NLL_FAMILY, NLL_KERNEL and NLL_KERNEL_GETTER and
+// include this file for the Matern fronts.  (Three instantiations of a
+// template body in one file were tried first: the compiler then allocates
+// every one of them differently, the RBF front at 80 VGPRs and 240 B of
+// scratch where it has 72 and none alone.)
+#ifndef NLL_FAMILY
+#define NLL_FAMILY GEOM_FAM_RBF
+#define NLL_KERNEL fused_expert_nll_kernel
+#define NLL_LAUNCHERS
+#endif
+
 extern "C" __global__ void __launch_bounds__(WG, 6)
-fused_expert_nll_kernel(const float* __restrict__ Xg,
-                        const float* __restrict__ yg,
-                        const float* __restrict__ scale,   // [d]
-                        const float amp, const float noise,
-                        const int k, const int d,
-                        double* __restrict__ out_nll,      // [E]
-                        double* __restrict__ out_sumW0,    // [E]
-                        double* __restrict__ out_trG,      // [E]
-                        double* __restrict__ out_contr,    // [E, d]
-                        int* __restrict__ out_bad,
-                        unsigned long long* __restrict__ out_clk) { // [E,20]
-                        // optional phase profiling (wall_clock64 boundaries)
+NLL_KERNEL(const float* __restrict__ Xg,
+           const float* __restrict__ yg,
+           const float* __restrict__ scale,   // [d]
+           const float amp, const float noise,
+           const int k, const int d,
+           double* __restrict__ out_nll,      // [E]
+           double* __restrict__ out_sumW0,    // [E]: sum(G o Kb)
+           double* __restrict__ out_trG,      // [E]
+           double* __restrict__ out_contr,    // [E, d]
+           int* __restrict__ out_bad,
+           unsigned long long* __restrict__ out_clk) { // [E,20]
+           // optional phase profiling (wall_clock64 boundaries)
+  constexpr int FAM = NLL_FAMILY;
   extern __shared__ char lds_raw[];
 #define PH(n) do { if (out_clk && threadIdx.x == 0) \
     out_clk[(size_t)blockIdx.x * 20 + (n)] = wall_clock64(); } while (0)
@@ -267,9 +297,16 @@ PH(1);
         const int gj = tj * 16 + l16;
         if (gi >= k || gj >= k || gj > gi) continue;
         float q = S.alpha[gi] + S.alpha[gj] - 2.0f * acc[u][r];
-        const float kb = __expf(-(q > 0.f ? q : 0.f));
-        S.A[(size_t)gi * SA + gj] = amp * kb + (gi == gj ? noise : 0.f);
-        if (gi != gj) S.A[(size_t)gj * SA + gi] = kb;   // Kb cache upper
+        if (FAM == GEOM_FAM_RBF) {
+          const float kb = __expf(-(q > 0.f ? q : 0.f));
+          S.A[(size_t)gi * SA + gj] = amp * kb + (gi == gj ? noise : 0.f);
+          if (gi != gj) S.A[(size_t)gj * SA + gi] = kb;   // Kb cache upper
+        } else {
+          S.A[(size_t)gi * SA + gj] =
+              amp * family_kb<FAM>(q) + (gi == gj ? noise : 0.f);
+          if (gi != gj)                                   // t cache upper
+            S.A[(size_t)gj * SA + gi] = sqrtf(q > 0.f ? q : 0.f);
+        }
       }
     }
   } else {
@@ -310,9 +347,16 @@ PH(1);
         const int gj = tj * 16 + l16;
         if (gi >= k || gj >= k || gj > gi) continue;
         float q = S.alpha[gi] + S.alpha[gj] - 2.0f * acc[r];
-        const float kb = __expf(-(q > 0.f ? q : 0.f));
-        S.A[(size_t)gi * SA + gj] = amp * kb + (gi == gj ? noise : 0.f);
-        if (gi != gj) S.A[(size_t)gj * SA + gi] = kb;   // Kb cache upper
+        if (FAM == GEOM_FAM_RBF) {
+          const float kb = __expf(-(q > 0.f ? q : 0.f));
+          S.A[(size_t)gi * SA + gj] = amp * kb + (gi == gj ? noise : 0.f);
+          if (gi != gj) S.A[(size_t)gj * SA + gi] = kb;   // Kb cache upper
+        } else {
+          S.A[(size_t)gi * SA + gj] =
+              amp * family_kb<FAM>(q) + (gi == gj ? noise : 0.f);
+          if (gi != gj)                                   // t cache upper
+            S.A[(size_t)gj * SA + gi] = sqrtf(q > 0.f ? q : 0.f);
+        }
       }
     }
   }
@@ -407,7 +451,9 @@ PH(5);
   }
 
 PH(6);
-    // ---- W: W0 = (aa^T - K^-1) o Kb, in place + mirror; trG, sumW0 ---
+    // ---- W: W = (aa^T - K^-1) o Kd, in place + mirror; trG, and
+    // sumW0 = sum (aa^T - K^-1) o Kb.  RBF: Kd = Kb, read from the cache.
+    // Matern: t from the cache, one exp for Kb and Kd (diagonal: t = 0).
   double trg_part = 0.0, sw_part = 0.0;
   {
     const int nlow = k * (k + 1) / 2;
@@ -415,13 +461,22 @@ PH(6);
       int a, b;
       tri_decode(f, a, b);
       const float g = S.alpha[a] * S.alpha[b] - S.A[(size_t)a * SA + b];
-      const float kb = (a == b) ? 1.0f : S.A[(size_t)b * SA + a];
-      const float w = g * kb;
+      float w, gkb;                         // g * Kd, g * Kb
+      if (FAM == GEOM_FAM_RBF) {
+        const float kb = (a == b) ? 1.0f : S.A[(size_t)b * SA + a];
+        w = g * kb;
+        gkb = w;
+      } else {
+        float kb, kd;
+        family_kb_kd<FAM>((a == b) ? 0.0f : S.A[(size_t)b * SA + a], kb, kd);
+        w = g * kd;
+        gkb = g * kb;
+      }
       if (a == b) {
         trg_part += (double)g;
-        sw_part += (double)w;
+        sw_part += (double)gkb;
       } else {
-        sw_part += 2.0 * (double)w;
+        sw_part += 2.0 * (double)gkb;
       }
       S.A[(size_t)a * SA + b] = w;
       if (a != b) S.A[(size_t)b * SA + a] = w;
@@ -524,6 +579,31 @@ PH(8);
     out_sumW0[e] = sumW0;
     out_trG[e] = trG;
   }
+#undef PH
+}
+
+typedef void (*nll_kernel_t)(
+    const float*, const float*, const float*, float, float, int, int,
+    double*, double*, double*, double*, int*, unsigned long long*);
+
+#ifndef NLL_LAUNCHERS
+
+// a Matern translation unit: hand its front to the launchers
+extern "C" const void* NLL_KERNEL_GETTER() { return (const void*)NLL_KERNEL; }
+
+#else   // the RBF translation unit: the launchers of every family
+
+extern "C" const void* nll_kernel_m32();   // expert_nll_m32.hip
+extern "C" const void* nll_kernel_m52();   // expert_nll_m52.hip
+
+// the front of a family code; null for an unknown one
+static nll_kernel_t nll_kernel_of(int family) {
+  switch (family) {
+    case GEOM_FAM_RBF: return fused_expert_nll_kernel;
+    case GEOM_FAM_M32: return (nll_kernel_t)nll_kernel_m32();
+    case GEOM_FAM_M52: return (nll_kernel_t)nll_kernel_m52();
+  }
+  return nullptr;
 }
 
 // dynamic LDS of a launch; 0 when the shape is not supported
@@ -542,10 +622,13 @@ extern "C" hipError_t launch_fused_expert_nll(
     const float* X, const float* y, const float* scale,
     float amp, float noise, int E, int k, int d,
     double* out_nll, double* out_sumW0, double* out_trG, double* out_contr,
-    int* out_bad, unsigned long long* out_clk, hipStream_t stream) {
+    int* out_bad, unsigned long long* out_clk, int family,
+    hipStream_t stream) {
+  const nll_kernel_t kern = nll_kernel_of(family);
+  if (!kern) return hipErrorInvalidValue;
   const size_t lds = nll_launch_lds(k, d);
   if (!lds) return hipErrorInvalidConfiguration;
-  hipLaunchKernelGGL(fused_expert_nll_kernel, dim3(E), dim3(WG), lds, stream,
+  hipLaunchKernelGGL(kern, dim3(E), dim3(WG), lds, stream,
                      X, y, scale, amp, noise, k, d,
                      out_nll, out_sumW0, out_trG, out_contr, out_bad,
                      out_clk);
@@ -554,9 +637,13 @@ extern "C" hipError_t launch_fused_expert_nll(
 
 // workgroups of the kernel the runtime keeps resident per CU at the block
 // size and dynamic LDS launch_fused_expert_nll uses for (k, d)
-extern "C" hipError_t fused_expert_nll_resident_wgs(int k, int d, int* out) {
+extern "C" hipError_t fused_expert_nll_resident_wgs(int k, int d, int family,
+                                                    int* out) {
+  const nll_kernel_t kern = nll_kernel_of(family);
+  if (!kern) return hipErrorInvalidValue;
   const size_t lds = nll_launch_lds(k, d);
   if (!lds) return hipErrorInvalidConfiguration;
-  return hipOccupancyMaxActiveBlocksPerMultiprocessor(
-      out, fused_expert_nll_kernel, WG, lds);
+  return hipOccupancyMaxActiveBlocksPerMultiprocessor(out, kern, WG, lds);
 }
+
+#endif  // NLL_LAUNCHERS

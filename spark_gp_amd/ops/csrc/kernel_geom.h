@@ -12,6 +12,48 @@
 #define GEOM_HD
 #endif
 
+// ---- covariance families (expert_nll.hip, cross_syrk.hip) -----------------
+// A kernel is instantiated per family: Kb(q) over the scaled squared distance
+// q = ||x'_a - x'_b||^2, t = sqrt(q) (family_kb, family_kb_kd below):
+//   RBF         Kb = e^-q                Kd = -dKb/dq = e^-q
+//   Matern 3/2  Kb = (1 + t) e^-t        Kd = e^-t / 2
+//   Matern 5/2  Kb = (1 + t + t^2/3) e^-t   Kd = (1 + t) e^-t / 6
+#define GEOM_FAM_RBF 0
+#define GEOM_FAM_M32 1
+#define GEOM_FAM_M52 2
+
+static inline bool geom_family_ok(long family) {
+  return family >= GEOM_FAM_RBF && family <= GEOM_FAM_M52;
+}
+
+#ifdef __HIPCC__
+// Kb at a q that may carry a small negative rounding residue
+template <int FAM>
+__device__ __forceinline__ float family_kb(const float q) {
+  const float qc = q > 0.f ? q : 0.f;
+  if (FAM == GEOM_FAM_RBF) return __expf(-qc);
+  const float t = sqrtf(qc);
+  const float e = __expf(-t);
+  if (FAM == GEOM_FAM_M32) return (1.0f + t) * e;
+  return (1.0f + t + t * t * (1.0f / 3.0f)) * e;
+}
+
+// Matern only (FAM is GEOM_FAM_M32 or GEOM_FAM_M52): Kb and Kd from
+// t = sqrt(q), one exp for both
+template <int FAM>
+__device__ __forceinline__ void family_kb_kd(const float t, float& kb,
+                                             float& kd) {
+  const float e = __expf(-t);
+  if (FAM == GEOM_FAM_M32) {
+    kb = (1.0f + t) * e;
+    kd = 0.5f * e;
+  } else {
+    kb = (1.0f + t + t * t * (1.0f / 3.0f)) * e;
+    kd = (1.0f + t) * e * (1.0f / 6.0f);
+  }
+}
+#endif
+
 // ---- fused expert kernels (expert_nll.hip, laplace.hip) -------------------
 // Every LDS region is padded to 16 B so the vectorized dots can assume
 // aligned bases.

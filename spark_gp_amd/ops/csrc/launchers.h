@@ -11,14 +11,17 @@
 extern "C" {
 #endif
 
+// `family`: a GEOM_FAM_* code of kernel_geom.h; a launcher given an unknown
+// one returns hipErrorInvalidValue.
+
 // ---- expert_nll.hip -------------------------------------------------------
 hipError_t launch_fused_expert_nll(
     const float* X, const float* y, const float* scale, float amp,
     float noise, int E, int k, int d, double* out_nll, double* out_sumW0,
     double* out_trG, double* out_contr, int* out_bad,
-    unsigned long long* out_clk, hipStream_t stream);
+    unsigned long long* out_clk, int family, hipStream_t stream);
 
-hipError_t fused_expert_nll_resident_wgs(int k, int d, int* out);
+hipError_t fused_expert_nll_resident_wgs(int k, int d, int family, int* out);
 
 // ---- laplace.hip ----------------------------------------------------------
 hipError_t launch_fused_laplace_newton(
@@ -37,13 +40,14 @@ hipError_t launch_fused_laplace_evidence(
 hipError_t launch_cross_kernel_tile(
     const float* X, const float* A, const float* s2v, float amp, int c,
     int m, int d, void* out, void* out_lo, void* out_t, void* out_lo_t,
-    int out_is_bf16, const float* yv, double* Ky, hipStream_t stream);
+    int out_is_bf16, const float* yv, double* Ky, int family,
+    hipStream_t stream);
 
 hipError_t launch_cross_mfma(const float* Xs, const float* As,
                              const float* nx, const float* na, float amp,
                              int c, int m, int d, void* out_bfT,
                              void* out_loT, const float* yv, double* Ky,
-                             hipStream_t stream);
+                             int family, hipStream_t stream);
 
 hipError_t launch_syrk_bf16(const void* KcT, const void* KlT, int c, int m,
                             int cpitch, int split_k, float* KK,
@@ -57,7 +61,7 @@ hipError_t launch_syrk_bf16_sync(const void* KcT, const void* KlT, int c,
 hipError_t launch_syrk_fused_gen(
     const float* Xs, const float* As, const float* nx, const float* na,
     float amp, const float* yv, int c, int m, int d, int split_k,
-    double* Ky, float* KK, hipStream_t stream);
+    double* Ky, float* KK, int family, hipStream_t stream);
 
 hipError_t launch_colsum_gemv(const void* Kc, const float* y, int c, int m,
                               double* Ky, hipStream_t stream);

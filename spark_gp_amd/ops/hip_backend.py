@@ -16,7 +16,9 @@ import numpy as np
 import torch
 
 from ..kernels.base import Kernel
-from ..kernels.compiled import CompiledKernel, compile_kernel
+from ..kernels.compiled import (BASES, RBF_BASES, CompiledKernel,
+                                base_family, base_is_ard, base_nup,
+                                base_scale, compile_kernel)
 from .. import _hip_ext as ext
 from . import torch_backend
 from . import ppa_plan
@@ -24,18 +26,25 @@ from . import ppa_plan
 
 def _scale_vector(cs: CompiledKernel, theta: np.ndarray, d: int,
                   device, dtype=torch.float32) -> torch.Tensor:
-    if cs.base == 'ard':
-        s = np.asarray(theta[cs.base_idx], dtype=np.float64)
-    else:  # rbf
-        sigma = float(theta[cs.base_idx][0])
-        s = np.full(d, 1.0 / (math.sqrt(2.0) * sigma))
+    """Coordinate scale s of the base: the kernels work on x' = x o s with
+    q = ||x'_a - x'_b||^2 (kernels/compiled.py lists s per base)."""
+    s = base_scale(cs.base, theta[cs.base_idx], d)
     return torch.as_tensor(s, dtype=dtype, device=device)
 
 
-def _supports_expert(cs, X: torch.Tensor, kd_supported) -> bool:
-    """An RBF/ARD kernel on [E, k, d] fp32 experts whose (k, d) the fused
-    kernel's LDS budget takes (``kd_supported``: an ``ext.*_supported``)."""
-    if cs is None or cs.base not in ("ard", "rbf"):
+def _family_args(cs: CompiledKernel) -> tuple:
+    """The trailing ``family`` argument of an ext call, positional.  The RBF
+    family is every entry point's default and is left out, so an RBF call
+    is the call it was before the kernels knew other families."""
+    fam = base_family(cs.base)
+    return (fam,) if fam else ()
+
+
+def _supports_expert(cs, X: torch.Tensor, kd_supported, bases) -> bool:
+    """A kernel with one of ``bases`` on [E, k, d] fp32 experts whose (k, d)
+    the fused kernel's LDS budget takes (``kd_supported``: an
+    ``ext.*_supported``)."""
+    if cs is None or cs.base not in bases:
         return False
     if X.dtype != torch.float32 or X.dim() != 3:
         return False
@@ -44,7 +53,7 @@ def _supports_expert(cs, X: torch.Tensor, kd_supported) -> bool:
 
 
 def supports_nll(cs: CompiledKernel, X: torch.Tensor) -> bool:
-    return _supports_expert(cs, X, ext.fused_expert_nll_supported)
+    return _supports_expert(cs, X, ext.fused_expert_nll_supported, BASES)
 
 
 def nll_grad_compiled(cs: CompiledKernel, theta: np.ndarray,
@@ -54,8 +63,10 @@ def nll_grad_compiled(cs: CompiledKernel, theta: np.ndarray,
     C = cs.amp(theta)
     nu = cs.noise(theta)
     scale = _scale_vector(cs, theta, d, X.device)
+    # sumW0 = sum(G o Kb), contr_j = sum_ab (G o Kd)_ab (x_aj - x_bj)^2
     nll, sumW0, trG, contr, bad = ext.fused_expert_nll(
-        X, y.to(torch.float32), scale, float(C), float(nu))
+        X, y.to(torch.float32), scale, float(C), float(nu),
+        *_family_args(cs))
 
     # single device->host transfer for all reductions (one sync per eval)
     stats = torch.cat([nll.sum().reshape(1), sumW0.sum().reshape(1),
@@ -74,9 +85,14 @@ def nll_grad_compiled(cs: CompiledKernel, theta: np.ndarray,
     grad = np.zeros(cs.p)
     if cs.amp_idx is not None:
         grad[cs.amp_idx] = -0.5 * sumW0_t
-    if cs.base == 'ard':
+    nup = base_nup(cs.base)
+    if base_is_ard(cs.base):
         beta = np.asarray(theta[cs.base_idx], dtype=np.float64)
-        grad[cs.base_idx] = C * beta * contr_t
+        grad[cs.base_idx] = (nup or 1.0) * C * beta * contr_t
+    elif nup is not None:
+        length = float(theta[cs.base_idx][0])
+        grad[cs.base_idx.start] = (-(nup * C / length ** 3)
+                                   * float(contr_t.sum()))
     else:
         sigma = float(theta[cs.base_idx][0])
         grad[cs.base_idx.start] = -C / (2.0 * sigma ** 3) * float(contr_t.sum())
@@ -111,7 +127,9 @@ LAPLACE_MIN_TOL = float(os.environ.get("SPARK_GP_AMD_LAPLACE_MIN_TOL",
 
 
 def supports_laplace(cs: CompiledKernel, X: torch.Tensor) -> bool:
-    return _supports_expert(cs, X, ext.fused_laplace_newton_supported)
+    # laplace.hip is exp(-q) only
+    return _supports_expert(cs, X, ext.fused_laplace_newton_supported,
+                            RBF_BASES)
 
 
 def _fused_laplace(entry, cs: CompiledKernel, theta: np.ndarray,
@@ -143,7 +161,8 @@ def laplace_newton(cs: CompiledKernel, theta: np.ndarray, X: torch.Tensor,
 
 
 def supports_laplace_evidence(cs: CompiledKernel, X: torch.Tensor) -> bool:
-    return _supports_expert(cs, X, ext.fused_laplace_evidence_supported)
+    return _supports_expert(cs, X, ext.fused_laplace_evidence_supported,
+                            RBF_BASES)
 
 
 def laplace_evidence(cs: CompiledKernel, theta: np.ndarray, X: torch.Tensor,
@@ -187,7 +206,7 @@ def laplace_evidence(cs: CompiledKernel, theta: np.ndarray, X: torch.Tensor,
 
 def supports_ppa(kernel: Kernel, X: torch.Tensor) -> bool:
     cs = compile_kernel(kernel)
-    return (cs is not None and cs.base in ("ard", "rbf")
+    return (cs is not None and cs.base in BASES
             and X.dtype == torch.float32)
 
 
@@ -219,6 +238,7 @@ def kmn_knm_and_kmny(kernel: Kernel, active: torch.Tensor,
     n, d = X.shape
     m = active.shape[0]
     C = float(cs.amp(theta))
+    fam = _family_args(cs)
     s2 = _s2_vector(cs, theta, d, X.device)
     act32 = active.to(torch.float32).contiguous()
     y32 = y.to(torch.float32)
@@ -231,7 +251,7 @@ def kmn_knm_and_kmny(kernel: Kernel, active: torch.Tensor,
         for s in range(0, n, chunk_rows):
             e = min(n, s + chunk_rows)
             Kc = ext.cross_kernel_tile(X[s:e].contiguous(), act32, s2,
-                                       C, False, False)[0]
+                                       C, False, False, False, *fam)[0]
             K64 = Kc.double()
             KK64 += K64.transpose(0, 1) @ K64
             Ky += K64.transpose(0, 1) @ y[s:e].double()
@@ -260,13 +280,14 @@ def kmn_knm_and_kmny(kernel: Kernel, active: torch.Tensor,
             Xs = (X[s:e] * svec).contiguous()
             nx = (Xs * Xs).sum(-1).contiguous()
         if plan.generator == "fused":
-            ext.ppa_fused_acc(Xs, As, nx, na, C, yc, Ky, KK, plan.split_k)
+            ext.ppa_fused_acc(Xs, As, nx, na, C, yc, Ky, KK, plan.split_k,
+                              *fam)
             continue
         if plan.generator == "mfma":
-            KcT, KlT = ext.cross_mfma_ppa(Xs, As, nx, na, C, yc, Ky)
+            KcT, KlT = ext.cross_mfma_ppa(Xs, As, nx, na, C, yc, Ky, *fam)
         else:
             KcT, KlT = ext.cross_kernel_tile_ppa(X[s:e].contiguous(), act32,
-                                                 s2, C, yc, Ky)
+                                                 s2, C, yc, Ky, *fam)
         if plan.syrk == "sync":
             for tiles, nactive in sync_tiles:
                 ext.syrk_bf16_sync_acc(KcT, KlT, KK, tiles,
@@ -362,4 +383,5 @@ def cross_kernel(kernel: Kernel, Xtest: torch.Tensor,
     s2 = _s2_vector(cs, theta, d, Xtest.device)
     return ext.cross_kernel_tile(Xtest.to(torch.float32).contiguous(),
                                  Xtrain.to(torch.float32).contiguous(),
-                                 s2, float(C), False, False)[0].to(Xtest.dtype)
+                                 s2, float(C), False, False, False,
+                                 *_family_args(cs))[0].to(Xtest.dtype)

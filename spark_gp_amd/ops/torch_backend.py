@@ -23,7 +23,9 @@ import numpy as np
 import torch
 
 from ..kernels.base import Kernel, sqdist
-from ..kernels.compiled import CompiledKernel
+from ..kernels.compiled import (CompiledKernel, FAM_M32, FAM_M52, FAM_RBF,
+                                base_family, base_is_ard, base_nup,
+                                base_scale)
 
 
 def logdet_and_inv(K: torch.Tensor, force_lu: bool = False
@@ -67,8 +69,29 @@ def logdet_and_inv(K: torch.Tensor, force_lu: bool = False
 # Fused regression objective (compiled kernel canonical form)
 # ---------------------------------------------------------------------------
 
+def family_kb_kd(family: int, q: torch.Tensor):
+    """(Kb(q), Kd(q) = -dKb/dq) of a covariance family at the scaled squared
+    distance q >= 0 (kernels/matern.py has the table)."""
+    if family == FAM_RBF:
+        Kb = torch.exp(-q)
+        return Kb, Kb
+    t = torch.sqrt(q.clamp_min(0.0))
+    e = torch.exp(-t)
+    if family == FAM_M32:
+        return (1.0 + t) * e, 0.5 * e
+    if family == FAM_M52:
+        return (1.0 + t + t * t / 3.0) * e, (1.0 + t) * e / 6.0
+    raise ValueError(f"unknown covariance family {family}")
+
+
 def _base_matrices(cs: CompiledKernel, theta: np.ndarray, X: torch.Tensor):
-    """Kb = exp(-sq) for the canonical base; returns (Kb, sq_scaled, extras)."""
+    """Kb(q) of the canonical base over the scaled coordinates Xs = X o s;
+    returns (Kb, q, Xs)."""
+    if base_nup(cs.base) is not None:
+        s = base_scale(cs.base, theta[cs.base_idx], X.shape[-1])
+        Xs = X * torch.as_tensor(s, dtype=X.dtype, device=X.device)
+        sq = sqdist(Xs, Xs)
+        return family_kb_kd(base_family(cs.base), sq)[0], sq, Xs
     if cs.base == 'ard':
         beta = torch.as_tensor(theta[cs.base_idx], dtype=X.dtype, device=X.device)
         Xs = X * beta
@@ -93,7 +116,8 @@ def nll_grad_compiled(cs: CompiledKernel, theta: np.ndarray,
     (``regression/GaussianProcessRegression.scala:55-68``), computed WITHOUT
     materializing the [p, k, k] derivative tensor: the ARD/RBF derivative
     contraction reduces to two GEMMs per batch (see K5 fusion plan,
-    SURVEY.md §2.4)."""
+    SURVEY.md §2.4).  With Kd = -dKb/dq the general form is
+    grad = 1/2 C sum((G o Kd) dq/dtheta); Kd = Kb for the RBF family."""
     C = cs.amp(theta)
     nu = cs.noise(theta)
     Kb, sq, _ = _base_matrices(cs, theta, X)
@@ -110,7 +134,21 @@ def nll_grad_compiled(cs: CompiledKernel, theta: np.ndarray,
     grad = np.zeros(cs.p)
     if cs.amp_idx is not None:
         grad[cs.amp_idx] = float(-0.5 * W0.double().sum())
-    if cs.base == 'ard':
+    nup = base_nup(cs.base)
+    if nup is not None:
+        # Matérn: W = G o Kd; contr_j = sum_ab W_ab (x_aj - x_bj)^2 by the
+        # same two-GEMM contraction
+        W = G * family_kb_kd(base_family(cs.base), sq)[1]
+        r = W.sum(-1)
+        t1 = (X * X * r.unsqueeze(-1)).sum(-2)
+        t2 = (X * (W @ X)).sum(-2)
+        contr = (2.0 * t1 - 2.0 * t2).double().sum(0).cpu().numpy()  # [d]
+        if base_is_ard(cs.base):
+            grad[cs.base_idx] = nup * C * theta[cs.base_idx] * contr
+        else:
+            length = float(theta[cs.base_idx][0])
+            grad[cs.base_idx.start] = -(nup * C / length ** 3) * contr.sum()
+    elif cs.base == 'ard':
         beta = theta[cs.base_idx]
         r = W0.sum(-1)                                           # [E, k]
         t1 = (X * X * r.unsqueeze(-1)).sum(-2)                   # [E, d]
