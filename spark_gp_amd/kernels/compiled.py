@@ -13,16 +13,19 @@ and nu = const + sum of trainable white-noise hypers.  Six bases are
 recognised, each a function of q = ||(a - b) o s||^2 in coordinates scaled
 per dimension by s:
 
-    base       class               family       s_j
-    'rbf'      RBFKernel           exp(-q)      1 / (sqrt(2) sigma)
-    'ard'      ARDRBFKernel        exp(-q)      beta_j
-    'm32'      Matern32Kernel      Matérn 3/2   sqrt(3) / l
-    'ard_m32'  ARDMatern32Kernel   Matérn 3/2   sqrt(3) beta_j
-    'm52'      Matern52Kernel      Matérn 5/2   sqrt(5) / l
-    'ard_m52'  ARDMatern52Kernel   Matérn 5/2   sqrt(5) beta_j
+    base       class               family       c         s_j
+    'rbf'      RBFKernel           exp(-q)      1/sqrt(2) c / sigma
+    'ard'      ARDRBFKernel        exp(-q)      1         c beta_j
+    'm32'      Matern32Kernel      Matérn 3/2   sqrt(3)   c / l
+    'ard_m32'  ARDMatern32Kernel   Matérn 3/2   sqrt(3)   c beta_j
+    'm52'      Matern52Kernel      Matérn 5/2   sqrt(5)   c / l
+    'ard_m52'  ARDMatern52Kernel   Matérn 5/2   sqrt(5)   c beta_j
 
-(``base_family``, ``base_nup``, ``base_is_ard`` and ``base_scale`` below; the
-family functions Kb(q) and Kd(q) = -dKb/dq are in ``kernels/matern.py``.)  The
+(``base_family``, ``base_nup``, ``base_is_ard``, ``base_scale`` and its
+transposed Jacobian ``base_scale_grad`` below; the family functions Kb(q) and
+Kd(q) = -dKb/dq are in ``kernels/matern.py``.)  Every gradient over theta is
+assembled here, by ``CompiledKernel.assemble_grad``, from a gradient with
+respect to s, the amplitude and the noise.  The
 fused objective (torch batched or the hand-written HIP kernel) consumes this
 ``CompiledKernel`` and computes the per-expert negative log marginal
 likelihood *and its full gradient* without ever materializing the
@@ -88,6 +91,22 @@ def base_scale(base: str, theta_base, d: int) -> np.ndarray:
                    else math.sqrt(nup) / length)
 
 
+def base_scale_grad(base: str, theta_base, g_s) -> np.ndarray:
+    """Gradient over the base hypers of a function whose gradient over
+    s = base_scale(base, theta_base, d) is ``g_s`` [d]: the transpose of
+    base_scale's Jacobian, one entry per base hyper.  With c of the table,
+    s = c beta gives g_beta = c g_s and s_j = c / l gives
+    g_l = -(c / l^2) sum(g_s)."""
+    nup = base_nup(base)
+    g_s = np.asarray(g_s, dtype=np.float64)
+    if base_is_ard(base):
+        c = 1.0 if nup is None else math.sqrt(nup)
+        return c * g_s
+    c = math.sqrt(0.5 if nup is None else nup)
+    length = float(theta_base[0])
+    return np.array([-(c / length ** 2) * g_s.sum()])
+
+
 @dataclass
 class CompiledKernel:
     """Canonical form  C * base(theta_base) + nu * I.
@@ -109,6 +128,19 @@ class CompiledKernel:
 
     def noise(self, theta) -> float:
         return self.noise_const + sum(float(theta[i]) for i in self.noise_idx)
+
+    def assemble_grad(self, theta, g_scale, g_amp: float,
+                      g_noise: float) -> np.ndarray:
+        """The [p] gradient over theta from its gradient over the coordinate
+        scale s ([d]), the amplitude C and the noise nu."""
+        grad = np.zeros(self.p)
+        if self.amp_idx is not None:
+            grad[self.amp_idx] = g_amp
+        grad[self.base_idx] = base_scale_grad(self.base, theta[self.base_idx],
+                                              g_scale)
+        for i in self.noise_idx:
+            grad[i] += g_noise
+        return grad
 
 
 class _Acc:

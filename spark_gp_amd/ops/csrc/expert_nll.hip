@@ -140,6 +140,27 @@ __device__ inline float scaled_sqnorm(const float* __restrict__ x,
   return s;
 }
 
+// Phase B's epilogue for one element gi >= gj of the lower triangle at the
+// scaled squared distance q: K = amp Kb(q) + noise I into the lower half of
+// A, and in the mirrored upper element what phase H rebuilds Kb and Kd
+// from: Kb itself for the RBF family, t = sqrt(q) for the Matern ones.
+template <int FAM>
+__device__ __forceinline__ void nll_b_store(float* A, const int SA,
+                                            const int gi, const int gj,
+                                            const float q, const float amp,
+                                            const float noise) {
+  if (FAM == GEOM_FAM_RBF) {
+    const float kb = __expf(-(q > 0.f ? q : 0.f));
+    A[(size_t)gi * SA + gj] = amp * kb + (gi == gj ? noise : 0.f);
+    if (gi != gj) A[(size_t)gj * SA + gi] = kb;           // Kb cache upper
+  } else {
+    A[(size_t)gi * SA + gj] =
+        amp * family_kb<FAM>(q) + (gi == gj ? noise : 0.f);
+    if (gi != gj)                                         // t cache upper
+      A[(size_t)gj * SA + gi] = sqrtf(q > 0.f ? q : 0.f);
+  }
+}
+
 // MFMA k-steps whose global X fragments are fetched together, so that a
 // tile pays one memory latency per XCH*4 contraction indices
 #define XCH 4
@@ -296,17 +317,8 @@ PH(1);
         const int gi = ti * 16 + kg * 4 + r;
         const int gj = tj * 16 + l16;
         if (gi >= k || gj >= k || gj > gi) continue;
-        float q = S.alpha[gi] + S.alpha[gj] - 2.0f * acc[u][r];
-        if (FAM == GEOM_FAM_RBF) {
-          const float kb = __expf(-(q > 0.f ? q : 0.f));
-          S.A[(size_t)gi * SA + gj] = amp * kb + (gi == gj ? noise : 0.f);
-          if (gi != gj) S.A[(size_t)gj * SA + gi] = kb;   // Kb cache upper
-        } else {
-          S.A[(size_t)gi * SA + gj] =
-              amp * family_kb<FAM>(q) + (gi == gj ? noise : 0.f);
-          if (gi != gj)                                   // t cache upper
-            S.A[(size_t)gj * SA + gi] = sqrtf(q > 0.f ? q : 0.f);
-        }
+        const float q = S.alpha[gi] + S.alpha[gj] - 2.0f * acc[u][r];
+        nll_b_store<FAM>(S.A, SA, gi, gj, q, amp, noise);
       }
     }
   } else {
@@ -346,17 +358,8 @@ PH(1);
         const int gi = ti * 16 + kg * 4 + r;
         const int gj = tj * 16 + l16;
         if (gi >= k || gj >= k || gj > gi) continue;
-        float q = S.alpha[gi] + S.alpha[gj] - 2.0f * acc[r];
-        if (FAM == GEOM_FAM_RBF) {
-          const float kb = __expf(-(q > 0.f ? q : 0.f));
-          S.A[(size_t)gi * SA + gj] = amp * kb + (gi == gj ? noise : 0.f);
-          if (gi != gj) S.A[(size_t)gj * SA + gi] = kb;   // Kb cache upper
-        } else {
-          S.A[(size_t)gi * SA + gj] =
-              amp * family_kb<FAM>(q) + (gi == gj ? noise : 0.f);
-          if (gi != gj)                                   // t cache upper
-            S.A[(size_t)gj * SA + gi] = sqrtf(q > 0.f ? q : 0.f);
-        }
+        const float q = S.alpha[gi] + S.alpha[gj] - 2.0f * acc[r];
+        nll_b_store<FAM>(S.A, SA, gi, gj, q, amp, noise);
       }
     }
   }

@@ -1,14 +1,15 @@
 """Python wrapper over the hand-written CDNA4 HIP kernels (_hip_ext).
 
-Gradient assembly happens here (host-side chain rule over the kernel's raw
-contraction outputs), mirroring exactly the formulas of
-``torch_backend.nll_grad_compiled`` so the two backends are drop-in
-interchangeable and unit-diffable.
+Every compiled base is Kb(q) with q = ||(a - b) o s||^2: the kernels take the
+scale vector s and the family code, and return raw contractions.  This module
+turns those into a gradient over (s, amplitude, noise) and hands it to
+``CompiledKernel.assemble_grad`` (kernels/compiled.py), the one place that
+knows how s depends on a base's hypers — as ``torch_backend`` does, so the
+two backends are drop-in interchangeable and unit-diffable.
 """
 
 from __future__ import annotations
 
-import math
 import os
 from typing import Tuple
 
@@ -17,8 +18,7 @@ import torch
 
 from ..kernels.base import Kernel
 from ..kernels.compiled import (BASES, RBF_BASES, CompiledKernel,
-                                base_family, base_is_ard, base_nup,
-                                base_scale, compile_kernel)
+                                base_family, base_scale, compile_kernel)
 from .. import _hip_ext as ext
 from . import torch_backend
 from . import ppa_plan
@@ -30,14 +30,6 @@ def _scale_vector(cs: CompiledKernel, theta: np.ndarray, d: int,
     q = ||x'_a - x'_b||^2 (kernels/compiled.py lists s per base)."""
     s = base_scale(cs.base, theta[cs.base_idx], d)
     return torch.as_tensor(s, dtype=dtype, device=device)
-
-
-def _family_args(cs: CompiledKernel) -> tuple:
-    """The trailing ``family`` argument of an ext call, positional.  The RBF
-    family is every entry point's default and is left out, so an RBF call
-    is the call it was before the kernels knew other families."""
-    fam = base_family(cs.base)
-    return (fam,) if fam else ()
 
 
 def _supports_expert(cs, X: torch.Tensor, kd_supported, bases) -> bool:
@@ -62,11 +54,12 @@ def nll_grad_compiled(cs: CompiledKernel, theta: np.ndarray,
     E, k, d = X.shape
     C = cs.amp(theta)
     nu = cs.noise(theta)
-    scale = _scale_vector(cs, theta, d, X.device)
+    s = base_scale(cs.base, theta[cs.base_idx], d)
+    scale = torch.as_tensor(s, dtype=torch.float32, device=X.device)
     # sumW0 = sum(G o Kb), contr_j = sum_ab (G o Kd)_ab (x_aj - x_bj)^2
     nll, sumW0, trG, contr, bad = ext.fused_expert_nll(
         X, y.to(torch.float32), scale, float(C), float(nu),
-        *_family_args(cs))
+        family=base_family(cs.base))
 
     # single device->host transfer for all reductions (one sync per eval)
     stats = torch.cat([nll.sum().reshape(1), sumW0.sum().reshape(1),
@@ -82,23 +75,9 @@ def nll_grad_compiled(cs: CompiledKernel, theta: np.ndarray,
         return float("inf"), np.zeros(cs.p)
     contr_t = stats[5:]                               # [d]
 
-    grad = np.zeros(cs.p)
-    if cs.amp_idx is not None:
-        grad[cs.amp_idx] = -0.5 * sumW0_t
-    nup = base_nup(cs.base)
-    if base_is_ard(cs.base):
-        beta = np.asarray(theta[cs.base_idx], dtype=np.float64)
-        grad[cs.base_idx] = (nup or 1.0) * C * beta * contr_t
-    elif nup is not None:
-        length = float(theta[cs.base_idx][0])
-        grad[cs.base_idx.start] = (-(nup * C / length ** 3)
-                                   * float(contr_t.sum()))
-    else:
-        sigma = float(theta[cs.base_idx][0])
-        grad[cs.base_idx.start] = -C / (2.0 * sigma ** 3) * float(contr_t.sum())
-    if cs.noise_idx:
-        for i in cs.noise_idx:
-            grad[i] += -0.5 * trG_t
+    # dq/ds_j = 2 s_j (x_aj - x_bj)^2, so the gradient over s is C s o contr
+    grad = cs.assemble_grad(theta, g_scale=(C * s) * contr_t,
+                            g_amp=-0.5 * sumW0_t, g_noise=-0.5 * trG_t)
 
     if n_bad:
         # fp32 Cholesky broke down for these experts (huge-amplitude
@@ -183,20 +162,8 @@ def laplace_evidence(cs: CompiledKernel, theta: np.ndarray, X: torch.Tensor,
         return None
     logZ = float(stats[0])
     g = stats[2:]
-    gb, gamp, gnoise = g[:d], float(g[d]), float(g[d + 1])
-    out = np.zeros(cs.p)
-    if cs.amp_idx is not None:
-        out[cs.amp_idx] = gamp
-    if cs.base == "ard":
-        out[cs.base_idx] = gb
-    else:
-        sigma = float(theta[cs.base_idx][0])
-        # the kernel differentiates w.r.t. the uniform scale beta =
-        # 1/(sqrt(2) sigma); chain rule: dbeta/dsigma = -1/(sqrt(2) s^2)
-        out[cs.base_idx.start] = (-float(gb.sum())
-                                  / (math.sqrt(2.0) * sigma * sigma))
-    for i in cs.noise_idx:
-        out[i] += gnoise
+    # the kernel differentiates logZ w.r.t. the scale, amplitude and noise
+    out = cs.assemble_grad(theta, g[:d], float(g[d]), float(g[d + 1]))
     return float(-logZ), -out
 
 
@@ -238,7 +205,7 @@ def kmn_knm_and_kmny(kernel: Kernel, active: torch.Tensor,
     n, d = X.shape
     m = active.shape[0]
     C = float(cs.amp(theta))
-    fam = _family_args(cs)
+    fam = base_family(cs.base)
     s2 = _s2_vector(cs, theta, d, X.device)
     act32 = active.to(torch.float32).contiguous()
     y32 = y.to(torch.float32)
@@ -250,8 +217,8 @@ def kmn_knm_and_kmny(kernel: Kernel, active: torch.Tensor,
         KK64 = torch.zeros(m, m, dtype=torch.float64, device=X.device)
         for s in range(0, n, chunk_rows):
             e = min(n, s + chunk_rows)
-            Kc = ext.cross_kernel_tile(X[s:e].contiguous(), act32, s2,
-                                       C, False, False, False, *fam)[0]
+            Kc = ext.cross_kernel_tile(X[s:e].contiguous(), act32, s2, C,
+                                       False, False, False, family=fam)[0]
             K64 = Kc.double()
             KK64 += K64.transpose(0, 1) @ K64
             Ky += K64.transpose(0, 1) @ y[s:e].double()
@@ -281,13 +248,14 @@ def kmn_knm_and_kmny(kernel: Kernel, active: torch.Tensor,
             nx = (Xs * Xs).sum(-1).contiguous()
         if plan.generator == "fused":
             ext.ppa_fused_acc(Xs, As, nx, na, C, yc, Ky, KK, plan.split_k,
-                              *fam)
+                              family=fam)
             continue
         if plan.generator == "mfma":
-            KcT, KlT = ext.cross_mfma_ppa(Xs, As, nx, na, C, yc, Ky, *fam)
+            KcT, KlT = ext.cross_mfma_ppa(Xs, As, nx, na, C, yc, Ky,
+                                          family=fam)
         else:
             KcT, KlT = ext.cross_kernel_tile_ppa(X[s:e].contiguous(), act32,
-                                                 s2, C, yc, Ky, *fam)
+                                                 s2, C, yc, Ky, family=fam)
         if plan.syrk == "sync":
             for tiles, nactive in sync_tiles:
                 ext.syrk_bf16_sync_acc(KcT, KlT, KK, tiles,
@@ -381,7 +349,8 @@ def cross_kernel(kernel: Kernel, Xtest: torch.Tensor,
     d = Xtest.shape[-1]
     C = cs.amp(theta)
     s2 = _s2_vector(cs, theta, d, Xtest.device)
-    return ext.cross_kernel_tile(Xtest.to(torch.float32).contiguous(),
-                                 Xtrain.to(torch.float32).contiguous(),
-                                 s2, float(C), False, False, False,
-                                 *_family_args(cs))[0].to(Xtest.dtype)
+    Kc = ext.cross_kernel_tile(Xtest.to(torch.float32).contiguous(),
+                               Xtrain.to(torch.float32).contiguous(),
+                               s2, float(C), False, False, False,
+                               family=base_family(cs.base))[0]
+    return Kc.to(Xtest.dtype)

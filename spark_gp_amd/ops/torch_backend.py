@@ -24,8 +24,7 @@ import torch
 
 from ..kernels.base import Kernel, sqdist
 from ..kernels.compiled import (CompiledKernel, FAM_M32, FAM_M52, FAM_RBF,
-                                base_family, base_is_ard, base_nup,
-                                base_scale)
+                                base_family, base_scale)
 
 
 def logdet_and_inv(K: torch.Tensor, force_lu: bool = False
@@ -85,25 +84,20 @@ def family_kb_kd(family: int, q: torch.Tensor):
 
 
 def _base_matrices(cs: CompiledKernel, theta: np.ndarray, X: torch.Tensor):
-    """Kb(q) of the canonical base over the scaled coordinates Xs = X o s;
-    returns (Kb, q, Xs)."""
-    if base_nup(cs.base) is not None:
-        s = base_scale(cs.base, theta[cs.base_idx], X.shape[-1])
-        Xs = X * torch.as_tensor(s, dtype=X.dtype, device=X.device)
-        sq = sqdist(Xs, Xs)
-        return family_kb_kd(base_family(cs.base), sq)[0], sq, Xs
-    if cs.base == 'ard':
-        beta = torch.as_tensor(theta[cs.base_idx], dtype=X.dtype, device=X.device)
-        Xs = X * beta
-        sq = sqdist(Xs, Xs)
-    elif cs.base == 'rbf':
-        sigma = float(theta[cs.base_idx][0])
-        scale = 1.0 / (math.sqrt(2.0) * sigma)
-        Xs = X * scale
-        sq = sqdist(Xs, Xs)
-    else:
-        raise ValueError(f"unsupported base {cs.base}")
-    return torch.exp(-sq), sq, Xs
+    """Kb(q) and Kd(q) = -dKb/dq of the canonical base at
+    q = ||(a - b) o s||^2; returns (Kb, Kd, s) with s the fp64 [d] scale."""
+    s = base_scale(cs.base, theta[cs.base_idx], X.shape[-1])
+    Xs = X * torch.as_tensor(s, dtype=X.dtype, device=X.device)
+    Kb, Kd = family_kb_kd(base_family(cs.base), sqdist(Xs, Xs))
+    return Kb, Kd, s
+
+
+def _diff2_contraction(W: torch.Tensor, X: torch.Tensor) -> torch.Tensor:
+    """contr_j = sum_ab W_ab (x_aj - x_bj)^2 for symmetric W [E, k, k], as
+    two GEMMs instead of the [E, k, k, d] difference tensor; [E, d]."""
+    t1 = (X * X * W.sum(-1).unsqueeze(-1)).sum(-2)
+    t2 = (X * (W @ X)).sum(-2)
+    return 2.0 * t1 - 2.0 * t2
 
 
 def nll_grad_compiled(cs: CompiledKernel, theta: np.ndarray,
@@ -114,13 +108,14 @@ def nll_grad_compiled(cs: CompiledKernel, theta: np.ndarray,
 
     nll_e = 1/2 y^T K^-1 y + 1/2 log|K|;  grad_i = -1/2 sum(dK_i * (aa^T - K^-1))
     (``regression/GaussianProcessRegression.scala:55-68``), computed WITHOUT
-    materializing the [p, k, k] derivative tensor: the ARD/RBF derivative
+    materializing the [p, k, k] derivative tensor: the derivative
     contraction reduces to two GEMMs per batch (see K5 fusion plan,
-    SURVEY.md §2.4).  With Kd = -dKb/dq the general form is
-    grad = 1/2 C sum((G o Kd) dq/dtheta); Kd = Kb for the RBF family."""
+    SURVEY.md §2.4).  With Kd = -dKb/dq and dq/ds_j = 2 s_j (x_aj - x_bj)^2
+    the gradient over the scale is g_s = C s o contr, contr the contraction
+    of G o Kd; ``cs.assemble_grad`` maps it onto theta."""
     C = cs.amp(theta)
     nu = cs.noise(theta)
-    Kb, sq, _ = _base_matrices(cs, theta, X)
+    Kb, Kd, s = _base_matrices(cs, theta, X)
     k = X.shape[-2]
     K = C * Kb + nu * torch.eye(k, dtype=X.dtype, device=X.device)
 
@@ -129,46 +124,11 @@ def nll_grad_compiled(cs: CompiledKernel, theta: np.ndarray,
     nll = (0.5 * (y * alpha).sum(-1).double() + 0.5 * logdet.double()).sum()
 
     G = alpha.unsqueeze(-1) * alpha.unsqueeze(-2) - Kinv         # [E, k, k]
-    W0 = G * Kb                                                  # [E, k, k]
-
-    grad = np.zeros(cs.p)
-    if cs.amp_idx is not None:
-        grad[cs.amp_idx] = float(-0.5 * W0.double().sum())
-    nup = base_nup(cs.base)
-    if nup is not None:
-        # Matérn: W = G o Kd; contr_j = sum_ab W_ab (x_aj - x_bj)^2 by the
-        # same two-GEMM contraction
-        W = G * family_kb_kd(base_family(cs.base), sq)[1]
-        r = W.sum(-1)
-        t1 = (X * X * r.unsqueeze(-1)).sum(-2)
-        t2 = (X * (W @ X)).sum(-2)
-        contr = (2.0 * t1 - 2.0 * t2).double().sum(0).cpu().numpy()  # [d]
-        if base_is_ard(cs.base):
-            grad[cs.base_idx] = nup * C * theta[cs.base_idx] * contr
-        else:
-            length = float(theta[cs.base_idx][0])
-            grad[cs.base_idx.start] = -(nup * C / length ** 3) * contr.sum()
-    elif cs.base == 'ard':
-        beta = theta[cs.base_idx]
-        r = W0.sum(-1)                                           # [E, k]
-        t1 = (X * X * r.unsqueeze(-1)).sum(-2)                   # [E, d]
-        WX = W0 @ X                                              # [E, k, d]
-        t2 = (X * WX).sum(-2)                                    # [E, d]
-        gb = (C * (2.0 * t1 - 2.0 * t2).double().sum(0)).cpu().numpy() * beta
-        grad[cs.base_idx] = gb
-    else:  # rbf
-        sigma = float(theta[cs.base_idx][0])
-        # sum(W0 * sq_scaled) via the same two-GEMM contraction
-        Xs = X * (1.0 / (math.sqrt(2.0) * sigma))
-        r = W0.sum(-1)
-        t1 = (Xs * Xs * r.unsqueeze(-1)).sum(-2)
-        t2 = (Xs * (W0 @ Xs)).sum(-2)
-        s = float((2.0 * t1 - 2.0 * t2).double().sum())
-        grad[cs.base_idx.start] = -(C / sigma) * s
-    if cs.noise_idx:
-        trG = float(G.diagonal(dim1=-2, dim2=-1).double().sum())
-        for i in cs.noise_idx:
-            grad[i] += -0.5 * trG
+    contr = _diff2_contraction(G * Kd, X).double().sum(0).cpu().numpy()  # [d]
+    trG = float(G.diagonal(dim1=-2, dim2=-1).double().sum())
+    grad = cs.assemble_grad(
+        theta, g_scale=(C * s) * contr,
+        g_amp=float(-0.5 * (G * Kb).double().sum()), g_noise=-0.5 * trG)
     return float(nll), grad
 
 
@@ -341,21 +301,28 @@ def kmn_knm_and_kmny(kernel: Kernel, active: torch.Tensor,
     return KK, Ky
 
 
-def laplace_evidence_compiled(cs: CompiledKernel, theta: np.ndarray,
-                              X: torch.Tensor, y: torch.Tensor,
-                              f: torch.Tensor) -> Tuple[float, np.ndarray]:
-    """Algorithm 5.1 evidence + gradient at an already-converged latent f,
-    WITHOUT materializing the [E, p, k, k] derivative tensor (the K11
-    contraction fusion): for the canonical kernel
-    C*Kb(base) + nu*I the dK_i contractions reduce to batched GEMMs via the
-    regression path's identities with G := a a^T - R, and the dK_i matvecs
-    (s3) via  (dK v) = expand((x-x')^2) o Kc v  ->  Kc @ [v, X o v, X^2 o v].
-    """
+def laplace_evidence_experts(cs: CompiledKernel, theta: np.ndarray,
+                             X: torch.Tensor, y: torch.Tensor,
+                             f: torch.Tensor
+                             ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Per-expert Algorithm 5.1 evidence and gradient at an already-converged
+    latent f: (logZ [E], g [E, d + 2]) in fp64, g the gradient of logZ over
+    the coordinate scale s, then the amplitude, then the noise — the contract
+    of ``ext.fused_laplace_evidence``.
+
+    Computed WITHOUT materializing the [E, p, k, k] derivative tensor (the
+    K11 contraction fusion): for the canonical kernel
+    C*Kb(q) + nu*I, dK/ds_j = -2 s_j C Kd o (x_j - x'_j)^2, so the dK_j
+    contractions reduce to batched GEMMs via the regression path's identities
+    with G := a a^T - R, and the dK_j matvecs (s3) via
+    (dK_j v) = -2 s_j (C Kd) @ [v, X o v, X^2 o v] recombined."""
     C = cs.amp(theta)
     nu = cs.noise(theta)
-    Kb, _, Xs = _base_matrices(cs, theta, X)
+    Kb, Kd, s = _base_matrices(cs, theta, X)
     E, k = y.shape
+    d = X.shape[-1]
     dt, dev = X.dtype, X.device
+    s = torch.as_tensor(s, dtype=dt, device=dev)
     eyek = torch.eye(k, dtype=dt, device=dev)
     K = C * Kb + nu * eyek
 
@@ -387,56 +354,39 @@ def laplace_evidence_compiled(cs: CompiledKernel, theta: np.ndarray,
     # shared pieces: s1_i = 1/2 sum(G o dK_i) with G = a a^T - R;
     # s3_i = b_i - K R b_i with b_i = dK_i v
     G = a.unsqueeze(-1) * a.unsqueeze(-2) - R
-    W0 = G * Kb
-    Kc = C * Kb
-    grad = np.zeros(cs.p)
 
     def s2_dot_s3(Bmat):
         """sum_a s2_a (Bmat - K R Bmat)_a per trailing column -> [E, cols]"""
         return (s2.unsqueeze(-1) * (Bmat - KR @ Bmat)).sum(-2)
 
-    if cs.base == 'ard':
-        bt = torch.as_tensor(theta[cs.base_idx], dtype=dt, device=dev)
-        # sum(G o Kc o Delta_j^2) = C (2 t1 - 2 t2)_j
-        r = W0.sum(-1)
-        t1 = (X * X * r.unsqueeze(-1)).sum(-2)
-        t2 = (X * (W0 @ X)).sum(-2)
-        s1 = -bt * C * (2.0 * t1 - 2.0 * t2)     # [E, d]; dK_j has -2 beta_j
-        # one batched GEMM for all three dK_j-matvec ingredients
-        d = X.shape[-1]
-        U = Kc @ torch.cat([v.unsqueeze(-1), X * v.unsqueeze(-1),
-                            X * X * v.unsqueeze(-1)], dim=-1)
-        u0, U1, U2 = U[..., 0], U[..., 1:1 + d], U[..., 1 + d:]
-        Bm = -2.0 * bt * (X * X * u0.unsqueeze(-1) - 2.0 * X * U1 + U2)
-        grad[cs.base_idx] = (s1.double().sum(0)
-                             + s2_dot_s3(Bm).double().sum(0)).cpu().numpy()
-    else:  # rbf: dK/dsigma = C sqd_raw o Kb / sigma^3 = (2C/sigma) sq_s o Kb
-        sigma = float(theta[cs.base_idx][0])
-        r = W0.sum(-1)
-        t1 = (Xs * Xs * r.unsqueeze(-1)).sum(-2)
-        t2 = (Xs * (W0 @ Xs)).sum(-2)
-        # s1 = 1/2 * (2C/sigma) * sum(W0 o sq_scaled)
-        s1 = (C / sigma) * (2.0 * t1 - 2.0 * t2).sum(-1)         # [E]
-        d = Xs.shape[-1]
-        U = Kc @ torch.cat([v.unsqueeze(-1), Xs * v.unsqueeze(-1),
-                            Xs * Xs * v.unsqueeze(-1)], dim=-1)
-        u0, U1, U2 = U[..., 0], U[..., 1:1 + d], U[..., 1 + d:]
-        Bm = (2.0 / sigma) * ((Xs * Xs).sum(-1) * u0
-                              - 2.0 * (Xs * U1).sum(-1) + U2.sum(-1))
-        grad[cs.base_idx.start] = float(
-            s1.double().sum()
-            + s2_dot_s3(Bm.unsqueeze(-1)).squeeze(-1).double().sum())
-    if cs.amp_idx is not None:                   # dK/dC = Kb
-        s1a = (0.5 * (a.unsqueeze(-2) @ (Kb @ a.unsqueeze(-1))).reshape(E)
-               - 0.5 * (R * Kb).sum((-1, -2)))
-        Ba = Kb @ v.unsqueeze(-1)
-        grad[cs.amp_idx] = float(
-            s1a.double().sum()
-            + s2_dot_s3(Ba).squeeze(-1).double().sum())
-    for i in cs.noise_idx:                       # dK = I
-        s1n = (0.5 * (a * a).sum(-1)
-               - 0.5 * R.diagonal(dim1=-2, dim2=-1).sum(-1))
-        grad[i] += float(s1n.double().sum()
-                         + s2_dot_s3(v.unsqueeze(-1)).squeeze(-1)
-                         .double().sum())
+    # scale: s1_j = 1/2 sum(G o dK_j) = -s_j C contr_j
+    s1 = -s * C * _diff2_contraction(G * Kd, X)                  # [E, d]
+    # one batched GEMM for all three dK_j-matvec ingredients
+    U = (C * Kd) @ torch.cat([v.unsqueeze(-1), X * v.unsqueeze(-1),
+                              X * X * v.unsqueeze(-1)], dim=-1)
+    u0, U1, U2 = U[..., 0], U[..., 1:1 + d], U[..., 1 + d:]
+    Bm = -2.0 * s * (X * X * u0.unsqueeze(-1) - 2.0 * X * U1 + U2)
+    g_scale = s1.double() + s2_dot_s3(Bm).double()
+    # amplitude: dK/dC = Kb
+    s1a = (0.5 * (a.unsqueeze(-2) @ (Kb @ a.unsqueeze(-1))).reshape(E)
+           - 0.5 * (R * Kb).sum((-1, -2)))
+    g_amp = s1a.double() + s2_dot_s3(Kb @ v.unsqueeze(-1)).squeeze(-1).double()
+    # noise: dK/dnu = I
+    s1n = 0.5 * (a * a).sum(-1) - 0.5 * R.diagonal(dim1=-2, dim2=-1).sum(-1)
+    g_noise = s1n.double() + s2_dot_s3(v.unsqueeze(-1)).squeeze(-1).double()
+    return logZ, torch.cat([g_scale, g_amp.unsqueeze(-1),
+                            g_noise.unsqueeze(-1)], dim=-1)
+
+
+def laplace_evidence_compiled(cs: CompiledKernel, theta: np.ndarray,
+                              X: torch.Tensor, y: torch.Tensor,
+                              f: torch.Tensor) -> Tuple[float, np.ndarray]:
+    """Negative Laplace evidence summed over the expert batch and its
+    gradient over theta, at an already-converged latent f."""
+    logZ, g = laplace_evidence_experts(cs, theta, X, y, f)
+    d = X.shape[-1]
+    g = g.sum(0).cpu().numpy()
+    grad = cs.assemble_grad(theta, g[:d], float(g[d]), float(g[d + 1]))
     return float(-logZ.sum()), -grad
+
+

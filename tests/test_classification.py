@@ -166,8 +166,11 @@ def test_one_vs_rest_iris():
 
 def test_laplace_evidence_compiled_matches_generic():
     """K11 contraction-form evidence (no [E,p,k,k] tensor) vs the generic
-    materialized-derivative path, at a converged latent f."""
-    from spark_gp_amd.kernels import compile_kernel, WhiteNoiseKernel
+    materialized-derivative path, at a converged latent f, for all six
+    compiled bases."""
+    from spark_gp_amd.kernels import (ARDMatern32Kernel, ARDMatern52Kernel,
+                                      Matern32Kernel, Matern52Kernel,
+                                      WhiteNoiseKernel, compile_kernel)
     g = torch.Generator().manual_seed(0)
     for factory, theta in [
         (lambda: 1 * ARDRBFKernel(3) + Scalar(1e-2).const * EyeKernel(),
@@ -175,6 +178,16 @@ def test_laplace_evidence_compiled_matches_generic():
         (lambda: 1 * RBFKernel(0.7) + WhiteNoiseKernel(0.1, 0, 1)
          + Scalar(1e-3).const * EyeKernel(),
          np.array([0.9, 0.75, 0.12])),
+        (lambda: 1 * Matern32Kernel(0.7) + WhiteNoiseKernel(0.1, 0, 1)
+         + Scalar(1e-3).const * EyeKernel(),
+         np.array([0.9, 0.75, 0.12])),
+        (lambda: 1 * Matern52Kernel(0.7) + Scalar(1e-2).const * EyeKernel(),
+         np.array([1.1, 0.8])),
+        (lambda: 1 * ARDMatern32Kernel(3) + Scalar(1e-2).const * EyeKernel(),
+         np.array([1.1, 0.8, 1.2, 0.6])),
+        (lambda: 1 * ARDMatern52Kernel(3) + WhiteNoiseKernel(0.1, 0, 1)
+         + Scalar(1e-3).const * EyeKernel(),
+         np.array([0.9, 0.8, 1.2, 0.6, 0.12])),
     ]:
         X = torch.randn(4, 18, 3, generator=g, dtype=TD)
         y = (X.sum(-1) > 0).double()
@@ -183,6 +196,9 @@ def test_laplace_evidence_compiled_matches_generic():
         f = torch.zeros(4, 18, dtype=TD)
         nll_ref, grad_ref = tb.laplace_nll_grad(kern, theta, X, y, f, 1e-10)
         nll_c, grad_c = tb.laplace_evidence_compiled(cs, theta, X, y, f)
+        print(f"{cs.base}: nll rel {abs(nll_c - nll_ref) / abs(nll_ref):.2e}"
+              f" grad max|d|/max|g| "
+              f"{np.abs(grad_c - grad_ref).max() / np.abs(grad_ref).max():.2e}")
         assert nll_c == pytest.approx(nll_ref, rel=1e-6)
         np.testing.assert_allclose(grad_c, grad_ref, rtol=1e-5,
                                    atol=1e-6 * np.abs(grad_ref).max())

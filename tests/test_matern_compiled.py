@@ -16,8 +16,10 @@ from spark_gp_amd.kernels import (ARDMatern32Kernel, ARDMatern52Kernel,
                                   EyeKernel, Matern32Kernel, Matern52Kernel,
                                   RBFKernel, Scalar, WhiteNoiseKernel,
                                   compile_kernel, sqdist)
+from spark_gp_amd.kernels.compiled import BASES as COMPILED_BASES
 from spark_gp_amd.kernels.compiled import (FAM_M32, FAM_M52, base_family,
-                                           base_is_ard, base_nup, base_scale)
+                                           base_is_ard, base_nup, base_scale,
+                                           base_scale_grad)
 from spark_gp_amd.ops import hip_backend, torch_backend
 from tests.test_kernels import fd_gradient_check
 
@@ -106,6 +108,28 @@ def test_compiled_canonical_matches_tree(base, seed):
     canon = (cs.amp(theta) * Kb
              + cs.noise(theta) * torch.eye(n, dtype=X.dtype)).numpy()
     np.testing.assert_allclose(direct, canon, rtol=1e-12, atol=1e-14)
+
+
+@pytest.mark.parametrize("base", COMPILED_BASES)
+def test_base_scale_grad_is_the_transposed_jacobian(base):
+    """base_scale_grad(g_s) against central differences of g_s . base_scale
+    over the base hypers.  The map is linear or 1/length, so at a step of
+    1e-6 theta the truncation error is ~1e-12 relative and the rounding
+    error ~1e-10."""
+    d = 3
+    rng = np.random.default_rng(11)
+    theta = rng.uniform(0.5, 2.0, d if base_is_ard(base) else 1)
+    g_s = rng.standard_normal(d)
+    got = base_scale_grad(base, theta, g_s)
+    assert got.shape == theta.shape
+    want = np.empty_like(theta)
+    for i in range(theta.size):
+        h = np.zeros_like(theta)
+        h[i] = 1e-6 * theta[i]
+        want[i] = (g_s @ base_scale(base, theta + h, d)
+                   - g_s @ base_scale(base, theta - h, d)) / (2.0 * h[i])
+    print(f"{base}: max rel {np.max(np.abs(got - want) / np.abs(want)):.2e}")
+    np.testing.assert_allclose(got, want, rtol=1e-7)
 
 
 @pytest.mark.parametrize("base", list(BASES))

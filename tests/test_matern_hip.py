@@ -82,13 +82,13 @@ def test_fused_expert_nll_matern_vs_oracle(dev, ext, base, E, k, d):
     nll_o, grad_o = torch_backend.nll_grad_compiled(cs, theta, Xc, yc)
 
     # raw sumW0 is sum(G o Kb), not sum(G o Kd)
-    Kb, sq, _ = torch_backend._base_matrices(cs, theta, Xc)
+    Kb, Kd, _ = torch_backend._base_matrices(cs, theta, Xc)
     K = theta[0] * Kb + 1e-3 * torch.eye(k, dtype=torch.float64)
     Kinv = torch.linalg.inv(K)
     alpha = (Kinv @ yc.unsqueeze(-1)).squeeze(-1)
     G = alpha.unsqueeze(-1) * alpha.unsqueeze(-2) - Kinv
     sum_gkb = (G * Kb).sum((-1, -2)).numpy()                   # [E]
-    sum_gkd = (G * torch_backend.family_kb_kd(fam, sq)[1]).sum((-1, -2))
+    sum_gkd = (G * Kd).sum((-1, -2))
     got = sumW0.cpu().numpy()
     print(f"{base} {(E, k, d)}: nll rel {abs(nll_h - nll_o) / abs(nll_o):.2e}"
           f" grad max|d|/max|g| "

@@ -174,9 +174,9 @@ def test_ppa_stats_fused_vs_two_kernel(dev, ext, monkeypatch):
     class _Spy:
         def __getattr__(self, name):
             if name == "ppa_fused_acc":
-                def f(*a):
+                def f(*a, **kw):
                     calls.append(1)
-                    return real(*a)
+                    return real(*a, **kw)
                 return f
             return getattr(ext, name)
 

@@ -64,9 +64,9 @@ def _run_and_compare(dev, monkeypatch, n, m, d, env, **kw):
             if name not in _ENTRY_POINTS:
                 return attr
 
-            def counted(*a):
+            def counted(*a, **kw):
                 calls[name] += 1
-                return attr(*a)
+                return attr(*a, **kw)
             return counted
 
     monkeypatch.setattr(hip_backend, "ext", _Spy())
