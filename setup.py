@@ -25,6 +25,7 @@ ext = CUDAExtension(
         "spark_gp_amd/ops/csrc/expert_nll_m52.hip",
         "spark_gp_amd/ops/csrc/cross_syrk.hip",
         "spark_gp_amd/ops/csrc/laplace.hip",
+        "spark_gp_amd/ops/csrc/predict.hip",
         "spark_gp_amd/ops/csrc/big_chol.hip",
         "spark_gp_amd/ops/csrc/synth.hip",
     ],

@@ -115,21 +115,29 @@ class GaussianProcessClassificationModel:
         from scipy.special import ndtr
         return ndtr(z)
 
-    def _latent(self, X) -> Tuple[torch.Tensor, torch.Tensor]:
+    def _latent(self, X, stream: bool = False, chunk_rows: int = 262144
+                ) -> Tuple[torch.Tensor, torch.Tensor]:
+        """Latent (mean, var); ``stream=True`` bounds peak memory for any
+        number of rows (the raw predictor's ``predict``)."""
         Xt = torch.as_tensor(X, dtype=self.raw.active_set.dtype,
                              device=self.raw.active_set.device)
         if Xt.dim() == 1:
             Xt = Xt.unsqueeze(0)
+        if stream:
+            return self.raw.predict(Xt, with_var=True, stream=True,
+                                    chunk_rows=chunk_rows)
         return self.raw.predict(Xt, with_var=True)
 
-    def predict_raw(self, X) -> np.ndarray:
+    def predict_raw(self, X, stream: bool = False,
+                    chunk_rows: int = 262144) -> np.ndarray:
         """(-f, f) scores per row (``GaussianProcessClassifier.scala:153-156``)."""
-        f, _ = self._latent(X)
+        f, _ = self._latent(X, stream, chunk_rows)
         f = f.cpu().numpy()
         return np.stack([-f, f], axis=-1)
 
     def predict_proba(self, X, averaged: bool = False,
-                      quadrature_points: int = 32) -> np.ndarray:
+                      quadrature_points: int = 32, stream: bool = False,
+                      chunk_rows: int = 262144) -> np.ndarray:
         """[p(y=0), p(y=1)] per row.
 
         Default: sigmoid of the latent mean, matching the reference's
@@ -137,7 +145,7 @@ class GaussianProcessClassificationModel:
         integrates the sigmoid over the latent posterior with Gauss-Hermite
         quadrature — the capability the reference's dead ``Integrator``
         (``commons/util/Integrator.scala``) was built for."""
-        f, var = self._latent(X)
+        f, var = self._latent(X, stream, chunk_rows)
         if averaged:
             from ..utils.integrator import Integrator
             integ = Integrator(quadrature_points)
@@ -148,8 +156,9 @@ class GaussianProcessClassificationModel:
             p1 = self._squash(f).cpu().numpy()
         return np.stack([1.0 - p1, p1], axis=-1)
 
-    def predict(self, X) -> np.ndarray:
-        f, _ = self._latent(X)
+    def predict(self, X, stream: bool = False,
+                chunk_rows: int = 262144) -> np.ndarray:
+        f, _ = self._latent(X, stream, chunk_rows)
         return (f.cpu().numpy() > 0).astype(np.float64)
 
     def transform(self, X):

@@ -88,20 +88,27 @@ class GaussianProcessPoissonModel:
         self.raw = raw
         self._instr: Optional[Instrumentation] = None
 
-    def _latent(self, X) -> Tuple[torch.Tensor, torch.Tensor]:
+    def _latent(self, X, stream: bool = False, chunk_rows: int = 262144
+                ) -> Tuple[torch.Tensor, torch.Tensor]:
+        """Latent (mean, var); ``stream=True`` bounds peak memory for any
+        number of rows (the raw predictor's ``predict``)."""
         Xt = torch.as_tensor(X, dtype=self.raw.active_set.dtype,
                              device=self.raw.active_set.device)
         if Xt.dim() == 1:
             Xt = Xt.unsqueeze(0)
+        if stream:
+            return self.raw.predict(Xt, with_var=True, stream=True,
+                                    chunk_rows=chunk_rows)
         return self.raw.predict(Xt, with_var=True)
 
-    def predict(self, X, return_std: bool = False):
+    def predict(self, X, return_std: bool = False, stream: bool = False,
+                chunk_rows: int = 262144):
         """Posterior-expected count rate E[exp(f*)] = exp(mu + var/2).
 
         With ``return_std``: the posterior-PREDICTIVE count std via the law
         of total variance, Var[y*] = E[lambda] + Var[lambda] with lognormal
         latent moments (Var[lambda] = (exp(var) - 1) exp(2 mu + var))."""
-        mu, var = self._latent(X)
+        mu, var = self._latent(X, stream, chunk_rows)
         mu = mu.clamp(max=self.fmax)
         var = var.clamp_min(0.0)
         rate = torch.exp(mu + 0.5 * var)
@@ -111,9 +118,10 @@ class GaussianProcessPoissonModel:
         std = torch.sqrt(rate + var_lam)
         return rate.cpu().numpy(), std.cpu().numpy()
 
-    def predict_latent(self, X):
+    def predict_latent(self, X, stream: bool = False,
+                       chunk_rows: int = 262144):
         """(mean, var) of the latent log-rate."""
-        mu, var = self._latent(X)
+        mu, var = self._latent(X, stream, chunk_rows)
         return mu.cpu().numpy(), var.cpu().numpy()
 
     def transform(self, X):

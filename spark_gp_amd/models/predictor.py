@@ -26,14 +26,23 @@ class GaussianProjectedProcessRawPredictor:
         self.kernel = kernel
         self.active_set = active_set
 
-    def predict(self, X: torch.Tensor, with_var: bool = True
+    def predict(self, X: torch.Tensor, with_var: bool = True,
+                stream: bool = False, chunk_rows: int = 262144
                 ) -> Tuple[torch.Tensor, torch.Tensor]:
         """X: [t, d] -> (mean [t], var [t]).
 
         mean = cross . magicVector
         var  = k(x,x) + cross . magicMatrix . cross^T   (rowwise)
+
+        ``stream=True`` bounds peak memory independently of t
+        (``ops.predict_stream``): the fused HIP kernel where its gate allows,
+        else this computation over row chunks of ``chunk_rows``.
         """
         act = self.active_set.to(X.dtype).to(X.device)
+        if stream:
+            return ops.predict_stream(
+                self.kernel, X, act, self.magic_vector.to(X.device),
+                self.magic_matrix.to(X.device), with_var, chunk_rows)
         cross = ops.cross_kernel(self.kernel, X, act).double()
         mv = self.magic_vector.to(cross.device)
         mean = cross @ mv

@@ -63,22 +63,29 @@ class GaussianProcessRegressionModel:
         self.raw = raw
         self._instr: Optional[Instrumentation] = None
 
-    def predict(self, X, return_std: bool = False):
+    def predict(self, X, return_std: bool = False, stream: bool = False,
+                chunk_rows: int = 262144):
         """PPA mean (and optionally the predictive std).
 
         The reference's public ``predict`` keeps only the mean
         (``GaussianProcessRegression.scala:79-81``); the variance is exposed
-        here as an option since the raw predictor computes it anyway."""
+        here as an option since the raw predictor computes it anyway.
+        ``stream=True`` bounds peak memory for any number of rows (the raw
+        predictor's ``predict``)."""
         Xt = torch.as_tensor(X, dtype=self.raw.active_set.dtype,
                              device=self.raw.active_set.device)
         if Xt.dim() == 1:
             Xt = Xt.unsqueeze(0)
-        mean, var = self.raw.predict(Xt, with_var=return_std)
+        if stream:
+            mean, var = self.raw.predict(Xt, with_var=return_std,
+                                         stream=True, chunk_rows=chunk_rows)
+        else:
+            mean, var = self.raw.predict(Xt, with_var=return_std)
         if return_std:
             return (mean.cpu().numpy(),
                     torch.sqrt(var.clamp_min(0.0)).cpu().numpy())
         return mean.cpu().numpy()
 
-    def transform(self, X):
+    def transform(self, X, stream: bool = False, chunk_rows: int = 262144):
         """DataFrame-style alias of ``predict`` (Spark ``transform`` parity)."""
-        return self.predict(X)
+        return self.predict(X, stream=stream, chunk_rows=chunk_rows)

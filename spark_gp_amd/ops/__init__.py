@@ -19,7 +19,7 @@ import numpy as np
 import torch
 
 from ..kernels.base import Kernel
-from ..kernels.compiled import BASES, CompiledKernel
+from ..kernels.compiled import BASES, CompiledKernel, compile_kernel
 from . import torch_backend
 
 _hip = None
@@ -149,3 +149,34 @@ def cross_kernel(kernel: Kernel, Xtest: torch.Tensor, Xtrain: torch.Tensor):
     if hip is not None and hip.supports_ppa(kernel, Xtest):
         return hip.cross_kernel(kernel, Xtest, Xtrain)
     return kernel.cross_kernel(Xtest, Xtrain)
+
+
+def predict_stream(kernel: Kernel, X: torch.Tensor, active: torch.Tensor,
+                   mv: torch.Tensor, M: torch.Tensor, with_var: bool = True,
+                   chunk_rows: int = 262144):
+    """PPA mean [t] and (``with_var``) variance [t] in fp64 with peak memory
+    bounded independently of t: the fused HIP kernel (no [t, m] array at
+    all) where its gate takes the kernel tree and (m, d); otherwise the
+    staged cross-kernel / GEMV / quadratic form over row chunks of
+    ``chunk_rows`` — any tree, any m, and on CPU."""
+    cs = compile_kernel(kernel)
+    hip = (_backend_for("predict_stream", X)
+           if cs is not None and cs.base in BASES else None)
+    if hip is not None and hip.supports_predict(kernel, X, active.shape[0]):
+        return hip.predict(kernel, X, active, mv, M, with_var)
+    if chunk_rows < 1:
+        raise ValueError(f"chunk_rows must be >= 1, got {chunk_rows}")
+    t = X.shape[0]
+    mv = mv.to(X.device)
+    mean = torch.empty(t, dtype=torch.float64, device=X.device)
+    var = torch.empty_like(mean) if with_var else None
+    if with_var:
+        M = M.to(X.device)
+    for s in range(0, t, chunk_rows):
+        e = min(t, s + chunk_rows)
+        cross = cross_kernel(kernel, X[s:e], active).double()
+        mean[s:e] = cross @ mv
+        if with_var:
+            var[s:e] = (kernel.self_kernel(X[s:e]).double()
+                        + ((cross @ M) * cross).sum(-1))
+    return mean, var

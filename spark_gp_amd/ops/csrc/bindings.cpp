@@ -6,6 +6,7 @@
 
 #include <climits>
 #include <initializer_list>
+#include <tuple>
 #include <vector>
 
 #include "kernel_geom.h"
@@ -421,6 +422,49 @@ bool fused_laplace_evidence_supported(int64_t k, int64_t d) {
   return lap_lds_bytes((int)k, (int)d, 1) <= GEOM_LDS_MAX;
 }
 
+// K14: fused prediction (predict.hip).  mean = c mv and, with want_var,
+// var = kxx + rowsum((c M) o c) for c = amp Kb(q(X, A)), without a [t, m]
+// array in memory.  M is the symmetric magic matrix; returns (mean[t] f64,
+// var[t] f64 or None).
+bool ppa_predict_supported(int64_t m, int64_t d) {
+  return ppa_predict_supported_md((long)m, (long)d);
+}
+
+// test rows per block the launcher picks for m active points (0: refused)
+int64_t ppa_predict_tile_rows(int64_t m) {
+  return pp_tile_rows((long)m);
+}
+
+std::tuple<torch::Tensor, c10::optional<torch::Tensor>> ppa_predict(
+    torch::Tensor X, torch::Tensor A, torch::Tensor s2, double amp,
+    torch::Tensor mv, torch::Tensor M, double kxx, bool want_var,
+    int64_t family) {
+  check_family(family);
+  check_arg(X, "X", F32, {ANY, ANY});
+  const int64_t t = X.size(0), d = X.size(1);
+  check_arg(A, "A", F32, {ANY, d});
+  const int64_t m = A.size(0);
+  check_vec(s2, "s2", F32, d);
+  check_arg(mv, "mv", F64, {m});
+  check_arg(M, "M", F64, {m, m});
+  TORCH_CHECK(ppa_predict_supported(m, d), "A: unsupported (m, d) = (", m,
+              ", ", d, ") for ppa_predict; query ppa_predict_supported");
+  check_same_gpu({{&X, "X"}, {&A, "A"}, {&s2, "s2"}, {&mv, "mv"}, {&M, "M"}});
+  make_contiguous({&X, &A, &s2, &mv, &M});
+  auto mean = torch::empty({t}, like(X, F64));
+  c10::optional<torch::Tensor> var;
+  if (want_var) var = torch::empty({t}, like(X, F64));
+  check_hip(launch_ppa_predict(
+                X.data_ptr<float>(), A.data_ptr<float>(),
+                s2.data_ptr<float>(), (float)amp, mv.data_ptr<double>(),
+                M.data_ptr<double>(), kxx, (long)t, (int)m, (int)d,
+                mean.data_ptr<double>(),
+                want_var ? var->data_ptr<double>() : nullptr, (int)family,
+                current_stream()),
+            "ppa_predict");
+  return {mean, var};
+}
+
 // ---------------------------------------------------------------------------
 // K13: blocked fp64 Cholesky path (big_chol.hip) — host orchestration
 // ---------------------------------------------------------------------------
@@ -597,6 +641,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
           pybind11::arg("amp"), pybind11::arg("bf16_out"),
           pybind11::arg("hilo"), pybind11::arg("want_t") = false,
           pybind11::arg("family") = (int)GEOM_FAM_RBF);
+  mod.def("ppa_predict", &ppa_predict,
+          "fused cross kernel + predictive mean and variance (K14, CDNA4)",
+          pybind11::arg("X"), pybind11::arg("A"), pybind11::arg("s2"),
+          pybind11::arg("amp"), pybind11::arg("mv"), pybind11::arg("M"),
+          pybind11::arg("kxx"), pybind11::arg("want_var"),
+          pybind11::arg("family") = (int)GEOM_FAM_RBF);
+  mod.def("ppa_predict_supported", &ppa_predict_supported);
+  mod.def("ppa_predict_tile_rows", &ppa_predict_tile_rows,
+          "test rows per block of ppa_predict at m active points (0: none)");
   mod.def("syrk_bf16_sync_acc", &syrk_bf16_sync_acc,
           "k-synchronized persistent SYRK for large m (CDNA4)");
   mod.def("syrk_bf16_acc", &syrk_bf16_acc,

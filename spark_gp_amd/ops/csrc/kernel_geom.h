@@ -1,6 +1,6 @@
 // Kernel geometry shared by the device code and the host-side gates: the
 // LDS budgets of the fused expert kernels and the SYRK tile constants.
-// Included by expert_nll.hip, laplace.hip, cross_syrk.hip (hipcc) and by
+// Included by expert_nll.hip, laplace.hip, cross_syrk.hip, predict.hip (hipcc) and by
 // bindings.cpp (host compiler), so a *_supported() answer and the launch it
 // guards are computed by the same function.
 #pragma once
@@ -144,6 +144,52 @@ static GEOM_HD inline size_t lap_lds_bytes(int k, int d, int ev = 0) {
 }
 
 #define GEOM_LDS_MAX (160 * 1024)   // LDS per workgroup on gfx950
+
+// ---- fused prediction (predict.hip) ---------------------------------------
+// One block owns a tile of TR test rows and keeps their whole fp32 cross
+// row c[TR][m] in LDS; TR is the largest of 64 / 32 / 16 whose plan fits.
+#define PP_THREADS 512   // 8 waves
+#define PP_DBLK 32       // feature dims staged per pass
+#define PP_CB 128        // active-set rows staged per pass
+
+// m up to the 16-column MFMA tile; columns [m, mp) of c are zero
+static GEOM_HD inline int pp_mp(int m) {
+  return (m + 15) & ~15;
+}
+
+// row stride of the c tile in floats.  = 2 (mod 4): the A-fragment read
+// c[i][k0 + (l>>4)], i = l&15, then touches bank 2 i u + (l>>4) (mod 32)
+// with u odd: 32 distinct banks in each 32-lane group.
+static GEOM_HD inline int pp_cstr(int m) {
+  return pp_mp(m) + 2;
+}
+
+// LDS bytes of ppa_predict_kernel<., ., TR>; region order is its carve
+static GEOM_HD inline size_t pp_lds_bytes(int tr, int m) {
+  size_t off = 0;
+  off += a16(sizeof(double) * (PP_THREADS / 64) * (size_t)tr);   // red
+  off += a16(sizeof(float) * (size_t)tr * pp_cstr(m));           // c
+  off += a16(sizeof(float) * PP_CB * (PP_DBLK + 1));             // as
+  off += a16(sizeof(float) * (size_t)tr * (PP_DBLK + 1));        // xs
+  off += a16(sizeof(float) * PP_DBLK);                           // s2
+  return off;
+}
+
+#define PP_M_MAX 4096   // keeps every size above far inside int range
+
+// rows per block for an active set of m points: 64, 32 or 16; 0 if even
+// 16 rows do not fit.  d never enters: the features are staged PP_DBLK at
+// a time and the running q lives in the c tile.
+static GEOM_HD inline int pp_tile_rows(long m) {
+  if (m < 1 || m > PP_M_MAX) return 0;
+  for (int tr = 64; tr >= 16; tr >>= 1)
+    if (pp_lds_bytes(tr, (int)m) <= GEOM_LDS_MAX) return tr;
+  return 0;
+}
+
+static GEOM_HD inline bool ppa_predict_supported_md(long m, long d) {
+  return d >= 1 && d <= 65536 && pp_tile_rows(m) != 0;
+}
 
 // ---- SYRK kernels (cross_syrk.hip) ----------------------------------------
 #define SY_CT 256     // output tile edge (per block)

@@ -66,6 +66,13 @@ hipError_t launch_syrk_fused_gen(
 hipError_t launch_colsum_gemv(const void* Kc, const float* y, int c, int m,
                               double* Ky, hipStream_t stream);
 
+// ---- predict.hip ----------------------------------------------------------
+// var == nullptr: mean only (M is then not read)
+hipError_t launch_ppa_predict(
+    const float* X, const float* A, const float* s2v, float amp,
+    const double* mv, const double* M, double kxx, long t, int m, int d,
+    double* mean, double* var, int family, hipStream_t stream);
+
 // ---- big_chol.hip ---------------------------------------------------------
 hipError_t launch_dpotrf_diag(double* A, long m, int jb, double* Vout,
                               int* bad, hipStream_t stream);

@@ -342,6 +342,35 @@ def magic_vector_matrix(kernel: Kernel, KK: torch.Tensor, Ky: torch.Tensor,
     return mv, PDinv * nu - Kmminv
 
 
+def supports_predict(kernel: Kernel, X: torch.Tensor, m: int) -> bool:
+    """A canonical tree on [t, d] fp32 rows whose (m, d) the fused predict
+    kernel's LDS plan takes (``ext.ppa_predict_supported``)."""
+    cs = compile_kernel(kernel)
+    if cs is None or cs.base not in BASES:
+        return False
+    if X.dtype != torch.float32 or X.dim() != 2:
+        return False
+    return bool(ext.ppa_predict_supported(int(m), int(X.shape[1])))
+
+
+def predict(kernel: Kernel, X: torch.Tensor, active: torch.Tensor,
+            mv: torch.Tensor, M: torch.Tensor, with_var: bool = True):
+    """K14 in one launch (predict.hip): mean [t] and, with ``with_var``,
+    var [t] in fp64, with no [t, m] array in memory."""
+    cs = compile_kernel(kernel)
+    theta = kernel.get_hyperparameters()
+    d = X.shape[-1]
+    s2 = _s2_vector(cs, theta, d, X.device)
+    # k(x, x) of a canonical tree is the same for every row: amp + noise
+    kxx = float(kernel.self_kernel(torch.zeros(1, d, dtype=torch.float64))[0])
+    mean, var = ext.ppa_predict(
+        X, active.to(X.device, torch.float32), s2, float(cs.amp(theta)),
+        mv.to(X.device, torch.float64), M.to(X.device, torch.float64), kxx,
+        bool(with_var),
+        family=base_family(cs.base))
+    return mean, var
+
+
 def cross_kernel(kernel: Kernel, Xtest: torch.Tensor,
                  Xtrain: torch.Tensor) -> torch.Tensor:
     cs = compile_kernel(kernel)
