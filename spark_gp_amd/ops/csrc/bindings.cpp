@@ -370,6 +370,10 @@ void colsum_gemv_acc(torch::Tensor Kc, torch::Tensor y, torch::Tensor Ky) {
 // evidence pass follows in the same launch; returns (logz[E] f64,
 // grad[E, d+2] f64 — beta grads then amp then noise, all d(logZ)/d(theta)
 // un-negated —, iters[E] i32, bad[E] i32).
+// max_newton = 0 skips the Newton loop: f comes back bitwise unchanged and
+// iters = 0, and with EV = true the tail evaluates Algorithm 5.1 (logz and
+// grad) at the given latent, converged or not — the exit state is recomputed
+// at f, nothing is carried over from an iteration.
 template <bool EV>
 std::vector<torch::Tensor> fused_laplace(torch::Tensor X, torch::Tensor y,
                                          torch::Tensor f, torch::Tensor scale,

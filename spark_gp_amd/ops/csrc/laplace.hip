@@ -16,8 +16,9 @@
 //   accept / halve s, stop on |delta psi| <= tol or s <= tol
 //
 // Outputs: updated latent f (in place), psi, sum log diag L, per-expert
-// Newton iteration count, bad flag (fp32 breakdown -> host falls back to
-// the batched torch path for that expert).  In EV mode the Algorithm 5.1
+// Newton iteration count, bad flag (fp32 breakdown or a non-finite feature
+// -> host falls back to the batched torch path for that expert; its f is
+// left as given and its EV outputs are zero).  In EV mode the Algorithm 5.1
 // evidence + FULL gradient (K11) run in the same launch at the converged
 // latent (see the evidence tail below); outside EV mode — or on any bad
 // expert, or for tolerances under LAPLACE_MIN_TOL — the torch
@@ -147,9 +148,12 @@ fused_laplace_kernel(const float* __restrict__ Xg,   // [E, k, d]
   const int dp = (int)geom_dp4(d);
 
   // ---- stage X, y, f, s2 -------------------------------------------
+  bool xfin = true;
   for (int i = tid; i < k * d; i += WG) {
     int a = i / d, j = i - a * d;
-    S.X[a * dp + j] = Xe[i];
+    const float x = Xe[i];
+    xfin = xfin && isfinite(x);
+    S.X[a * dp + j] = x;
   }
   for (int i = tid; i < k; i += WG) {
     S.yb[i] = yg[(size_t)e * k + i];
@@ -160,8 +164,18 @@ fused_laplace_kernel(const float* __restrict__ Xg,   // [E, k, d]
     S.s2[j] = s * s;
     if (EV) S.betav[j] = s;
   }
-  if (tid == 0) *S.bad = 0;
+  if (tid == 0) {
+    *S.bad = 0;
+    S.misc[0] = 0.0;   // out_sumlogl of a launch that never factors
+  }
   __syncthreads();
+  // A non-finite feature is a non-finite breakdown (bad = 2), flagged here
+  // because an inf never reaches a pivot: its row of the cache is
+  // kb = exp(-inf) = 0, B stays finite, and the evidence tail then
+  // multiplies that 0 by the inf — a NaN gradient under bad = 0.  The
+  // barrier behind the cache build publishes the flag; the Newton loop and
+  // the tail are skipped and f is left alone.
+  if (!xfin) *S.bad = 2;
 
   // ---- Kb cache into A's STRICT UPPER (kb = exp(-q); kb_aa = 1) ----
   // Single-buffer design (round 2): the old separate full-K buffer cost
@@ -203,7 +217,8 @@ fused_laplace_kernel(const float* __restrict__ Xg,   // [E, k, d]
   double new_obj = -1.7976931348623157e308;   // -DBL_MAX, as the reference
   double step = 1.0;
   int it = 0;
-  for (; it < max_newton; ++it) {
+  const int nmax = *S.bad ? 0 : max_newton;   // block-uniform
+  for (; it < nmax; ++it) {
     // pi, w, sqw, b
     for (int i = tid; i < k; i += WG) {
       const float fi = S.fb[i];

@@ -204,6 +204,50 @@ def test_laplace_evidence_compiled_matches_generic():
                                    atol=1e-6 * np.abs(grad_ref).max())
 
 
+@pytest.mark.parametrize("base", ["ard", "rbf"])
+@pytest.mark.parametrize("k,d", [(7, 3), (33, 5), (65, 7)])
+def test_laplace_evidence_experts_matches_generic_unconverged(k, d, base):
+    """Pins the oracle of the GPU tests (tests/test_laplace_hip.py): the
+    per-expert ``laplace_evidence_experts`` in fp64, summed over experts and
+    assembled by ``cs.assemble_grad``, against the generic
+    materialized-derivative path evaluated at the same UNCONVERGED latent
+    (``newton=False``), with a signed ARD scale and all of amplitude, base
+    hypers and noise trainable."""
+    from tests.test_laplace_hip import evidence_case
+    c = evidence_case(k, d, base)
+    f = c.latents["unconverged"].double()
+    logZ, g = tb.laplace_evidence_experts(c.cs, c.theta, c.X64, c.y64, f)
+    assert logZ.shape == (c.E,) and g.shape == (c.E, d + 2)
+    gs = g.sum(0).numpy()
+    nll = -float(logZ.sum())
+    grad = -c.cs.assemble_grad(c.theta, gs[:d], float(gs[d]),
+                               float(gs[d + 1]))
+    f_in = f.clone()
+    nll_ref, grad_ref = tb.laplace_nll_grad(c.kern, c.theta, c.X64, c.y64,
+                                            f_in, 1e-12, newton=False)
+    assert torch.equal(f_in, f)
+    assert grad_ref.shape == (c.cs.p,)
+    np.testing.assert_allclose(nll, nll_ref, rtol=1e-9)
+    np.testing.assert_allclose(grad, grad_ref, rtol=1e-9)
+
+
+@pytest.mark.parametrize("start", ["zero", "warm"])
+@pytest.mark.parametrize("k,d", [(13, 5), (33, 5), (100, 8)])
+def test_written_out_newton_steps_match_generic_loop(k, d, start):
+    """Pins the one- and two-step Newton reference of the GPU tests against
+    the first iterations of the generic loop (both candidates accepted)."""
+    from tests.test_laplace_hip import step_case
+    c = step_case(k, d, start)
+    for n in (1, 2):
+        f = c.f0.double()
+        tb.laplace_nll_grad(c.kern, c.theta, c.X64, c.y64, f, 1e-12,
+                            max_newton_iter=n)
+        np.testing.assert_allclose(c.f64[n].numpy(), f.numpy(), rtol=1e-9,
+                                   atol=1e-11)
+        assert not torch.equal(c.f64[n], c.f0.double())
+    assert not torch.equal(c.f64[1], c.f64[2])
+
+
 def test_averaged_proba_shrinks_toward_half():
     """Gauss-Hermite averaging over the latent posterior must pull
     probabilities toward 0.5 relative to the plain sigmoid-of-mean

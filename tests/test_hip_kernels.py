@@ -343,7 +343,9 @@ def test_fused_laplace_newton_vs_torch(dev, ext):
     np.testing.assert_allclose(f_hip.cpu().numpy(), f_ref.numpy(),
                                rtol=2e-3, atol=2e-3)
 
-    # dispatched objective (fused pre-pass + torch evidence) vs pure torch
+    # dispatched objective vs pure torch: tol == LAPLACE_MIN_TOL, so the
+    # dispatcher takes the fully fused path (Newton and the Algorithm 5.1
+    # evidence in one launch), not a fused pre-pass with a torch evidence
     f1 = torch.zeros(E, k, device=dev)
     nll1, grad1 = ops.laplace_nll_grad(kernel, theta, X, y, f1, tol)
     nll2, grad2 = torch_backend.laplace_nll_grad(
