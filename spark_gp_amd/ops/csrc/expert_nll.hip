@@ -33,8 +33,11 @@
 //      (right-to-left column blocks, rows fully parallel:
 //       V_IJ = -(sum_{K>J} V_IK L_KJ) L_JJ^-1).
 //   E  alpha = V^T (V y);  nll = 1/2 y.alpha + 1/2 logdet
-//   L  lauum K^-1 = V^T V on f32 MFMA (masked fragments, register tiles
-//      across a barrier; strictly lower+diagonal so the Kb cache survives)
+//   L  lauum K^-1 = V^T V on f32 MFMA (masked fragments, fetched four
+//      steps at a time with no load under a lane condition; tile (ti, tj)
+//      summed from row 16 ti on, two tiles of a wave advanced alternately;
+//      register tiles across a barrier; strictly lower+diagonal so the Kb
+//      cache survives)
 //   W  W0 = (alpha alpha^T - K^-1) o Kd, Kd = -dKb/dq (RBF: Kd = Kb, from
 //      the upper-triangle cache); trG and sumW0 = sum (alpha alpha^T -
 //      K^-1) o Kb accumulated on the fly
@@ -75,6 +78,7 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdlib.h>
+#include <type_traits>
 
 #define WG 512
 #include "linalg_lds.h"
@@ -164,6 +168,50 @@ __device__ __forceinline__ void nll_b_store(float* A, const int SA,
 // MFMA k-steps whose global X fragments are fetched together, so that a
 // tile pays one memory latency per XCH*4 contraction indices
 #define XCH 4
+
+// NS k-steps of NT (one or two) 16x16 output tiles of phase L on
+// v_mfma_f32_16x16x4_f32, the fragments masked LDS reads of V (row stride
+// SA).  Step s of tile t contracts the rows c[t] + 4 s + kg (kg = lane >> 4,
+// c[t] the same in every lane) of the columns ga[t] (A fragment) and gb[t]
+// (B fragment); an element V[cc][g] is inside the mask where cc < k, g < k
+// and cc >= g.  All 2 NS NT fragments are fetched before the first MFMA: a
+// masked element reads index 0 (always inside the buffer) and is zeroed by
+// a select afterwards, so that no load sits under a lane condition (the
+// form assemble_diag_inverse uses: a conditional load is issued, and waited
+// for, in its own branch right before its MFMA).  The fragment index is a
+// scalar that moves with the step plus a vector that does not.  The MFMAs
+// run in ascending s; with two tiles they alternate, so that a tile's
+// accumulator chain never waits on its own previous MFMA.
+template <int NS, int NT>
+__device__ __forceinline__ void lauum_feed(mfma_f32x4* acc, const float* V,
+                                           const int SA, const int k,
+                                           const int kg, const int (&c)[NT],
+                                           const int (&ga)[NT],
+                                           const int (&gb)[NT]) {
+  float av[NT][NS], bv[NT][NS];
+  bool oa[NT][NS], ob[NT][NS];
+#pragma unroll
+  for (int s = 0; s < NS; ++s) {
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+      const int cs = c[t] + 4 * s, cc = cs + kg;
+      oa[t][s] = cc < k && ga[t] < k && cc >= ga[t];
+      ob[t][s] = cc < k && gb[t] < k && cc >= gb[t];
+      av[t][s] = V[oa[t][s] ? cs * SA + (kg * SA + ga[t]) : 0];
+      bv[t][s] = V[ob[t][s] ? cs * SA + (kg * SA + gb[t]) : 0];
+    }
+  }
+  // every load is issued before the first select waits for one
+  __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+  for (int s = 0; s < NS; ++s) {
+#pragma unroll
+    for (int t = 0; t < NT; ++t)
+      acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(
+          oa[t][s] ? av[t][s] : 0.f, ob[t][s] ? bv[t][s] : 0.f, acc[t],
+          0, 0, 0);
+  }
+}
 
 // The kernel is compiled once per covariance family (kernel_geom.h), one
 // front per translation unit: this file by itself gives the RBF front,
@@ -412,29 +460,46 @@ PH(5);
   {
     const int nt = (k + 15) / 16;
     const int ntri = nt * (nt + 1) / 2;
-    const int wave = tid >> 6;
+    // the wave index in an SGPR: tile indices and loop bounds are then
+    // scalar, and the tile loops branch on SCC, not on exec
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l16 = lane & 15, kg = lane >> 4;
     constexpr int MAXT = 5;                 // ceil(36 tiles / 8 waves)
+    // Tile (ti, tj), ti >= tj, has no unmasked A fragment before c = 16 ti,
+    // so its sum starts there (the steps left out add +0).  Fragments come
+    // in batches of XCH steps (lauum_feed above), and a wave's tiles go in
+    // pairs: the second of a pair lies in a later tile row, starts later
+    // and is the shorter one, so the pair runs together until the second
+    // ends.
     mfma_f32x4 acc[MAXT];                   // compile-time indexed only
 #pragma unroll
-    for (int u = 0; u < MAXT; ++u) {
-      acc[u] = {0.f, 0.f, 0.f, 0.f};
-      const int t = wave + u * (WG / 64);
-      if (t >= ntri) continue;
+    for (int u = 0; u < MAXT; ++u) acc[u] = {0.f, 0.f, 0.f, 0.f};
+    // tiles u and u + 1 of this wave, u a compile-time constant
+    const auto pair = [&](auto uc) {
+      constexpr int u = decltype(uc)::value;
+      const int t = wave + u * (WG / 64), t2 = t + WG / 64;
+      if (t >= ntri) return;
       int ti, tj;
       tri_decode(t, ti, tj);
-      const int gi = ti * 16 + l16;         // A-fragment column of V
-      const int gj = tj * 16 + l16;         // B-fragment column of V
-      for (int c0 = 0; c0 < k; c0 += 4) {
-        const int cc = c0 + kg;
-        const float av = (cc < k && gi < k && cc >= gi)
-                             ? S.A[(size_t)cc * SA + gi] : 0.f;
-        const float bv = (cc < k && gj < k && cc >= gj)
-                             ? S.A[(size_t)cc * SA + gj] : 0.f;
-        acc[u] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bv, acc[u],
-                                                      0, 0, 0);
+      int c0 = 16 * ti;
+      const int gi = ti * 16 + l16, gj = tj * 16 + l16;
+      if constexpr (u + 1 < MAXT) {
+        if (t2 < ntri) {
+          int ti2, tj2;
+          tri_decode(t2, ti2, tj2);
+          const int ga[2] = {gi, ti2 * 16 + l16};
+          const int gb[2] = {gj, tj2 * 16 + l16};
+          for (int c2 = 16 * ti2; c2 < k; c0 += 4 * XCH, c2 += 4 * XCH)
+            lauum_feed<XCH, 2>(&acc[u], S.A, SA, k, kg, {c0, c2}, ga, gb);
+        }
       }
-    }
+      for (; c0 < k; c0 += 4 * XCH)
+        lauum_feed<XCH, 1>(&acc[u], S.A, SA, k, kg, {c0}, {gi}, {gj});
+    };
+    pair(std::integral_constant<int, 0>{});
+    pair(std::integral_constant<int, 2>{});
+    pair(std::integral_constant<int, 4>{});
+    static_assert(MAXT <= 6, "phase L pairs its tiles by hand");
     __syncthreads();                        // all V reads complete
 #pragma unroll
     for (int u = 0; u < MAXT; ++u) {
