@@ -4,10 +4,11 @@ Usage (GPU box):  python scripts/bench_syrk.py [rows] [m]
 Prints achieved bf16 TFLOP/s (counting all 3 hi/lo MFMA products) and the
 max relative error of KK against a torch fp64 reference.
 
-    python scripts/bench_syrk.py ROWS M --fused [D]
+    python scripts/bench_syrk.py ROWS M --fused [D] [--gen f16|f32]
 times one whole PPA chunk both ways on the same inputs, alternating: the
-staged pair (cross_mfma_ppa + syrk_bf16_acc) against ppa_fused_acc over a
-split_k sweep (the table in profiles/PROFILES.md, round 3).
+staged pair (cross_mfma_ppa + syrk_bf16_acc) against ppa_fused_acc (with the
+f16 generator, or the fp32 one) over a split_k sweep (the tables in
+profiles/PROFILES.md, rounds 3 and 12).
 """
 import os
 import sys
@@ -43,6 +44,11 @@ def _fused_ab(rows, m, d):
     Ky = torch.zeros(m, dtype=torch.float64, device=dev)
     tiles = syrk_tile_count(m)
     sk_pair = syrk_staged_split_k(m)
+    # --gen f16|f32: the fused kernel's generator; the bound is taken once
+    # here so the timed calls do not reduce the inputs again
+    gen = sys.argv[sys.argv.index("--gen") + 1] if "--gen" in sys.argv \
+        else "f16"
+    absmax = float(torch.maximum(Xs.abs().max(), As.abs().max()))
 
     def pair():
         KcT, KlT = ext.cross_mfma_ppa(Xs, As, nx, na, 1.3, y, Ky)
@@ -56,7 +62,7 @@ def _fused_ab(rows, m, d):
         torch.cuda.synchronize()
         return (time.perf_counter() - t0) / reps * 1e3
 
-    print(f"fused A/B rows={rows} m={m} d={d} tiles={tiles} "
+    print(f"fused A/B rows={rows} m={m} d={d} tiles={tiles} gen={gen} "
           f"pair split_k={sk_pair} fused default split_k="
           f"{ppa_fused_split_k(m)}")
     if not ext.ppa_fused_supported(m, d):
@@ -71,7 +77,8 @@ def _fused_ab(rows, m, d):
     pair()
     for sk in sks:
         def fused():
-            ext.ppa_fused_acc(Xs, As, nx, na, 1.3, y, Ky, KK, sk)
+            ext.ppa_fused_acc(Xs, As, nx, na, 1.3, y, Ky, KK, sk, gen=gen,
+                              absmax=absmax)
         fused()
         tp, tf = [], []
         for _ in range(3):                # alternate

@@ -327,11 +327,28 @@ bool ppa_fused_supported(int64_t m, int64_t d) {
   return ntile * (ntile + 1) / 2 <= SY_SPLITK_MAX_TILES;
 }
 
+//
+// gen selects how the blocks form x'.a': "f16" from two-term f16 images of
+// the coordinates on the 16-bit matrix pipe, "f32" on the fp32 one, "auto"
+// f16 when the coordinates are inside its range.  The f16 images overflow at
+// 65504, so "f16" and "auto" need a bound on |Xs| and |As|: absmax when the
+// caller has one (hip_backend takes it once per accumulation), else the
+// binding reduces both tensors itself, which synchronises with the device.
+// "auto" falls back to f32 at or above SF_F16_ABS_LIMIT, "f16" is refused
+// there; a NaN bound counts as out of range.
+//
+// partials: scratch for the k-slices' tiles (ppa_fused_partials_numel
+// elements or more, contents irrelevant), so a caller with many chunks
+// allocates it once; allocated here when absent.
 void ppa_fused_acc(torch::Tensor Xs, torch::Tensor As, torch::Tensor nx,
                    torch::Tensor na, double amp, torch::Tensor y,
                    torch::Tensor Ky, torch::Tensor KK, int64_t split_k,
-                   int64_t family) {
+                   int64_t family, const std::string& gen,
+                   c10::optional<double> absmax,
+                   c10::optional<torch::Tensor> partials) {
   check_family(family);
+  TORCH_CHECK(gen == "auto" || gen == "f16" || gen == "f32",
+              "gen must be \"auto\", \"f16\" or \"f32\", got \"", gen, "\"");
   check_ppa_inputs(Xs, As, nx, na, y, Ky);
   const int c = Xs.size(0), m = As.size(0), d = Xs.size(1);
   TORCH_CHECK(ppa_fused_supported(m, d), "As: unsupported (m, d) for "
@@ -339,15 +356,41 @@ void ppa_fused_acc(torch::Tensor Xs, torch::Tensor As, torch::Tensor nx,
   check_arg(KK, "KK", F32, {m, m}, true);
   TORCH_CHECK(split_k >= 1 && split_k <= 65535,
               "split_k out of range [1, 65535]: ", split_k);
+  const int64_t part_floats = (int64_t)sf_partial_floats(c, m, split_k);
+  if (partials.has_value()) {
+    check_dtype(*partials, "partials", F32, true);
+    TORCH_CHECK(partials->numel() >= part_floats, "partials must have at "
+                "least ", part_floats, " elements for this (c, m, split_k), "
+                "got ", partials->numel());
+  }
   check_same_gpu({{&Xs, "Xs"}, {&As, "As"}, {&nx, "nx"}, {&na, "na"},
-                  {&y, "y"}, {&Ky, "Ky"}, {&KK, "KK"}});
+                  {&y, "y"}, {&Ky, "Ky"}, {&KK, "KK"},
+                  {partials.has_value() ? &*partials : nullptr, "partials"}});
   if (c == 0) return;
+  torch::Tensor part = partials.has_value()
+                           ? *partials
+                           : torch::empty({part_floats}, like(KK, F32));
+  bool gen_f16 = false;
+  if (gen != "f32") {
+    double bound;
+    if (absmax.has_value()) {
+      bound = *absmax;
+    } else {
+      const auto [xlo, xhi] = at::aminmax(Xs);
+      const auto [alo, ahi] = at::aminmax(As);
+      bound = torch::stack({-xlo, xhi, -alo, ahi}).max().item<double>();
+    }
+    gen_f16 = bound < SF_F16_ABS_LIMIT;   // false for NaN
+    TORCH_CHECK(gen_f16 || gen == "auto", "gen=\"f16\" needs |Xs| and |As| "
+                "below ", SF_F16_ABS_LIMIT, ", got ", bound);
+  }
   make_contiguous({&Xs, &As, &nx, &na, &y});
   check_hip(launch_syrk_fused_gen(
                 Xs.data_ptr<float>(), As.data_ptr<float>(),
                 nx.data_ptr<float>(), na.data_ptr<float>(), (float)amp,
                 y.data_ptr<float>(), c, m, d, (int)split_k,
-                Ky.data_ptr<double>(), KK.data_ptr<float>(), (int)family,
+                Ky.data_ptr<double>(), KK.data_ptr<float>(),
+                part.data_ptr<float>(), (int)family, gen_f16 ? 1 : 0,
                 current_stream()),
             "ppa_fused_acc");
 }
@@ -593,6 +636,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.attr("SY_BK") = (int)SY_BK;
   mod.attr("SF_DMAX") = (int)SF_DMAX;
   mod.attr("SY_SPLITK_MAX_TILES") = (int)SY_SPLITK_MAX_TILES;
+  mod.attr("SF_F16_ABS_LIMIT") = (double)SF_F16_ABS_LIMIT;
   // covariance family codes of the `family` arguments below
   mod.attr("FAM_RBF") = (int)GEOM_FAM_RBF;
   mod.attr("FAM_M32") = (int)GEOM_FAM_M32;
@@ -633,7 +677,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
           "KK += K^T K, Ky += K^T y with K_nm generated in the SYRK (CDNA4)",
           pybind11::arg("Xs"), pybind11::arg("As"), pybind11::arg("nx"), pybind11::arg("na"), pybind11::arg("amp"), pybind11::arg("y"),
           pybind11::arg("Ky"), pybind11::arg("KK"), pybind11::arg("split_k"),
-          pybind11::arg("family") = (int)GEOM_FAM_RBF);
+          pybind11::arg("family") = (int)GEOM_FAM_RBF,
+          pybind11::arg("gen") = "auto",
+          pybind11::arg("absmax") = pybind11::none(),
+          pybind11::arg("partials") = pybind11::none());
+  mod.def("ppa_fused_partials_numel",
+          [](int64_t c, int64_t m, int64_t split_k) {
+            return (int64_t)sf_partial_floats(c, m, split_k);
+          },
+          "fp32 elements of ppa_fused_acc's partials buffer",
+          pybind11::arg("c"), pybind11::arg("m"), pybind11::arg("split_k"));
   mod.def("ppa_fused_supported", &ppa_fused_supported);
   mod.def("cross_kernel_tile_ppa", &cross_kernel_tile_ppa,
           "transposed hi/lo tiles + fused K^T y accumulation (CDNA4)",

@@ -13,7 +13,9 @@
 //  * syrk_fused_gen     — the round-3 PPA default (d <= 32, <= 256 tiles):
 //    syrk_bf16's tiles and products with the K_nm operand windows
 //    GENERATED in the block by cross_mfma's formula instead of staged
-//    through HBM; Ky += K^T y fused into the diagonal tiles.
+//    through HBM (x'.a' from split-f16 operands on the 16-bit matrix pipe by
+//    default); Ky += K^T y fused into the diagonal tiles; the k-slices'
+//    tiles are summed by syrk_fused_reduce in a fixed order, not by atomics.
 //  * syrk_bf16_sync     — k-synchronized persistent SYRK for large m
 //    (one block owns one tile; bounded best-effort pacing).
 //  * colsum_gemv        — Ky[m] += K_nm^T y (fp64 accumulation;
@@ -21,8 +23,9 @@
 //    standalone op).
 //
 // The three SYRK kernels are one tile body with three fronts.  Defined once
-// and shared: the bf16 product pass (syrk_mfma_pass), the tile epilogue
-// (syrk_epilogue, atomic or plain), the k-slice range (syrk_kslice), and for
+// and shared: the bf16 product pass (syrk_mfma_pass), the tile epilogue of the
+// staged kernels (syrk_epilogue, atomic or plain; syrk_fused_gen stores
+// partial tiles instead), the k-slice range (syrk_kslice), and for
 // the two kernels that stage operands from HBM the lane decomposition,
 // the load / LDS-write / prefetch pipeline and its k-loop
 // (syrk_staged_steps).  The K_nm value formula (knm_value) and the hi/lo
@@ -66,6 +69,23 @@ __device__ __forceinline__ float knm_value(const float nx, const float na,
 __device__ __forceinline__ void split_hilo(const float v, bf16& hi, bf16& lo) {
   hi = (bf16)v;
   lo = (bf16)(v - (float)hi);
+}
+
+// Two-term f16 image of a scaled coordinate for syrk_fused_gen's f16
+// generator: v ~ hi + lo * 2^-11 carries 22 significand bits.  hi is zeroed
+// below the f16 normal range, so no result depends on how the matrix core
+// treats f16 subnormal inputs: such a v goes entirely into lo (absolute error
+// below 2e-8).  |v| must be below the f16 range (65504): the host gates on
+// 2^15.
+typedef _Float16 f16;
+typedef __attribute__((ext_vector_type(2))) _Float16 f16x2;
+typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
+#define SF_LO_SCALE 2048.0f               // 2^11
+#define SF_LO_INV (1.0f / 2048.0f)
+
+__device__ __forceinline__ void split_f16(const float v, f16& hi, f16& lo) {
+  hi = (fabsf(v) < 0x1p-14f) ? (f16)0.f : (f16)v;
+  lo = (f16)((v - (float)hi) * SF_LO_SCALE);
 }
 
 // ---------------------------------------------------------------------------
@@ -432,8 +452,8 @@ __device__ __forceinline__ bool syrk_kslice(const int c, const int split_k,
 // one bf16 product pass acc += at^T bt over a k-block, in two b-halves of
 // 16 INDEPENDENT MFMAs (no accumulator chaining between consecutive
 // issues); fb covers 4 of the 8 column tiles at a time to stay inside the
-// register budget.  (This and syrk_epilogue take the lane's offsets as four
-// ints, not as a SyLane: syrk_fused_gen calls them too, see its note.)
+// register budget.  (This takes the lane's offsets as four ints, not as a
+// SyLane: syrk_fused_gen calls it too, see its note.)
 __device__ __forceinline__ void syrk_mfma_pass(SyAcc& acc, const bf16* at,
                                                const bf16* bt, const int wr,
                                                const int wc, const int l16,
@@ -653,16 +673,24 @@ syrk_bf16_kernel(const bf16* __restrict__ KcT,  // [m, cpitch] hi^T
 // (2 x 2 B x c x m per chunk, re-read once per tile that uses a window),
 // every block recomputes the two 32 x 256 operand windows of its k-step:
 //
-//  * tile geometry, wave layout, accumulators, the three bf16 MFMA passes
-//    and the atomic epilogue are the shared tile body above, as in
-//    syrk_bf16_kernel<true>;
+//  * tile geometry, wave layout, accumulators and the three bf16 MFMA passes
+//    are the shared tile body above, as in syrk_bf16_kernel<true>;
 //  * where that kernel prefetches k-block kb+1 into registers around the
 //    MFMA phase of kb, this one generates it: wave w owns the 16-column
 //    groups 2w and 2w+1 of each window and both 16-row halves of the
-//    k-block, i.e. 8 fragments (4 on a diagonal tile) of
-//    mfma_f32_16x16x4_f32 over d in cross_mfma_kernel's d order, then that
-//    kernel's knm_value() and split_hilo(), so the values are the numbers
-//    it would store;
+//    k-block, i.e. 8 fragments (4 on a diagonal tile) of x'.a', then
+//    cross_mfma_kernel's knm_value() and split_hilo();
+//  * x'.a' comes from one of two generators, a compile-time switch (G16) on
+//    the same tile function.  f32: mfma_f32_16x16x4_f32 over d in
+//    cross_mfma_kernel's d order, so the values are the numbers that kernel
+//    would store.  f16 (the default inside its range): x' and a' are each
+//    split into two f16 terms (split_f16: 22 bits) and x'.a' = xh.ah +
+//    2^-11 (xh.al + xl.ah) is three mfma_f32_16x16x32_f16 chained on one fp32
+//    accumulator, smallest products first: 3 x 16 cycles per fragment for 8 x
+//    32.  The dropped xl.al term is 2^-22 relative, the size of an fp32
+//    rounding of the sum; the values are fp32-class but not bit-equal to
+//    cross_mfma_kernel's (measured against fp64: PROFILES.md round 12).  d <=
+//    32 is exactly the K extent of that MFMA; d-slots >= d hold zeros;
 //  * the f32 D layout (col = lane&15, row = (lane>>4)*4 + r) hands each
 //    lane 4 consecutive k of one column: one 8-B store per operand into the
 //    k-major LDS tiles (80-B column pitch: conflict-free per half-wave),
@@ -674,7 +702,12 @@ syrk_bf16_kernel(const bf16* __restrict__ KcT,  // [m, cpitch] hi^T
 //    (143 VGPRs of scratch next to the 128 accumulators).  Both fp32 images
 //    are stored fragment-major (slot kgrp*8 + kc holds d-index kgrp + 4*kc),
 //    so a lane fetches 4 consecutive kc with one conflict-free b128 read
-//    while the MFMAs still run over d in cross_mfma_kernel's order;
+//    while the MFMAs still run over d in cross_mfma_kernel's order.  The f16
+//    generator keeps the same rows and pitch (144 B) and stores hi (64 B)
+//    and lo (64 B) of a row side by side in d order, split once per block
+//    for A' and at the staging write for X': a lane's 8 consecutive d of one
+//    image are one b128 read, the 16x16x32 operand layout, at the bank
+//    offsets of the fp32 reads (36 dwords x l16), so equally conflict-free;
 //  * X', nx and y of one k-step (32 x 34 floats) are staged through LDS,
 //    prefetched one step ahead in registers — the only global reads in
 //    the loop;
@@ -683,15 +716,22 @@ syrk_bf16_kernel(const bf16* __restrict__ KcT,  // [m, cpitch] hi^T
 //    are the only blocks that accumulate Ky += K^T y for their window: from
 //    the fp32 values before the split, folded into fp64 registers every
 //    k-step, one fp64 atomic per column per block;
-//  * the grid holds the upper-triangle tiles only; blocks are independent.
+//  * the grid holds the upper-triangle tiles only; blocks are independent;
+//  * a block ends by storing its 256 x 256 accumulator with plain 16-B stores
+//    into its own slot of `partials` ([k-slice][tile], fragment-major, 1 KB
+//    per wave store); syrk_fused_reduce_kernel, next in the stream, adds the
+//    slices of each element to KK in ascending slice order and gives an
+//    off-diagonal element and its mirror the same sum.  No fp32 atomics: KK
+//    does not vary from run to run, and off-diagonal tiles are bit-symmetric
+//    for every split_k.  Only Ky keeps atomics.
 //
 // d <= SF_DMAX: the LDS budget above has room for 32 d-slots per row.
-// Resources on gfx950 (hipcc -O3, -Rpass-analysis=kernel-resource-usage):
-// 234 VGPRs, 0 AGPRs, 0 B scratch, no spills, 160,256 B LDS,
-// 2 waves/SIMD (one 8-wave block per CU).
+// Resources on gfx950 (hipcc -O3, -Rpass-analysis=kernel-resource-usage),
+// all six instances (3 families x 2 generators): 232 VGPRs, 0 AGPRs, 0 B
+// scratch, no spills, 160,256 B LDS, 2 waves/SIMD (one 8-wave block per CU).
 //
-// This kernel sits 22 VGPRs under the limit and its register allocation
-// follows small changes of form.  It shares syrk_mfma_pass, syrk_epilogue,
+// This kernel sits 24 VGPRs under the limit and its register allocation
+// follows small changes of form.  It shares syrk_mfma_pass,
 // syrk_kslice, knm_value and split_hilo with the other kernels; the
 // compiler emits the same instructions for it with or without that sharing.
 // Three small pieces stay written out in sf_tile because every shared form
@@ -704,7 +744,9 @@ syrk_bf16_kernel(const bf16* __restrict__ KcT,  // [m, cpitch] hi^T
                       // 36*l16 mod 64 is a permutation of 4-bank blocks, so
                       // the A-fragment reads (l16 rows x 4 k) are conflict-free
 
-template <bool DIAG, int FAM>
+#define SF_HSTR (2 * SF_XSTR)   // the same pitch in f16 units (144 B)
+
+template <bool DIAG, int FAM, bool G16>
 __device__ __forceinline__ void
 sf_tile(const float* __restrict__ Xs, const float* __restrict__ As,
         const float* __restrict__ nx, const float* __restrict__ na,
@@ -714,7 +756,7 @@ sf_tile(const float* __restrict__ Xs, const float* __restrict__ As,
         bf16* __restrict__ lt, bf16* __restrict__ rt,
         bf16* __restrict__ ltl, bf16* __restrict__ rtl,
         float* __restrict__ xs, float* __restrict__ aw,
-        double* __restrict__ Ky, float* __restrict__ KK) {
+        double* __restrict__ Ky, float* __restrict__ part) {
   constexpr int NG = DIAG ? 2 : 4;        // generated column groups per wave
   // sy_lane() and sy_zero(), written out (see the note above)
   const int tid = threadIdx.x;
@@ -746,32 +788,59 @@ sf_tile(const float* __restrict__ Xs, const float* __restrict__ As,
   // A' windows -> LDS once per block, fragment-major: slot kgrp*8 + kc holds
   // d-index kgrp + 4*kc, so a lane's 4 consecutive kc are one b128 read.
   // Columns >= m and d-slots >= d are zeros.
+  // G16: the same rows hold the two f16 images instead, in d order: hi at
+  // f16 slots 0..31 and lo at 32..63 (128 B of the 144-B pitch), so a lane's
+  // 8 consecutive d of either image are one b128 read at the same bank
+  // offsets (36 dwords x l16) as the fp32 reads.
+  f16* const awh = (f16*)aw;
+  f16* const xsh = (f16*)xs;
   for (int f = tid; f < (DIAG ? 1 : 2) * SY_CT * SF_DMAX; f += SY_WG) {
     const int w = f / (SY_CT * SF_DMAX);
     const int col = (f / SF_DMAX) % SY_CT, q = f % SF_DMAX;
     const int gc = (w ? j0 : i0) + col;
-    aw[(w * SY_CT + col) * SF_XSTR + (q & 3) * 8 + (q >> 2)] =
-        (gc < m && q < d) ? As[(size_t)gc * d + q] : 0.f;
+    const float v = (gc < m && q < d) ? As[(size_t)gc * d + q] : 0.f;
+    if constexpr (G16) {
+      f16 vh, vl;
+      split_f16(v, vh, vl);
+      awh[(w * SY_CT + col) * SF_HSTR + q] = vh;
+      awh[(w * SY_CT + col) * SF_HSTR + SF_DMAX + q] = vl;
+    } else {
+      aw[(w * SY_CT + col) * SF_XSTR + (q & 3) * 8 + (q >> 2)] = v;
+    }
   }
 
   // X' staging (same fragment-major slots, + nx at 32, y at 33): thread ->
   // (row, d-slots xsl and xsl+16); lanes 0/1 of each 16 also carry the
-  // row's nx / y.  Rows >= c stage zeros.
+  // row's nx / y.  Rows >= c stage zeros.  G16: d-slots 2 xsl and 2 xsl + 1,
+  // split here, so each image takes one packed 4-B store; nx and y stay fp32
+  // in the same two slots.
   const int xrow = tid >> 4, xsl = tid & 15;
+  const int xq0 = G16 ? 2 * xsl : xsl, xq1 = G16 ? 2 * xsl + 1 : xsl + 16;
   float px0, px1, pe;
   auto gload = [&](int kb) {
     const int gr = kb * SY_BK + xrow;
     const bool ok = gr < c;
-    px0 = (ok && xsl < d) ? Xs[(size_t)gr * d + xsl] : 0.f;
-    px1 = (ok && xsl + 16 < d) ? Xs[(size_t)gr * d + xsl + 16] : 0.f;
+    px0 = (ok && xq0 < d) ? Xs[(size_t)gr * d + xq0] : 0.f;
+    px1 = (ok && xq1 < d) ? Xs[(size_t)gr * d + xq1] : 0.f;
     pe = 0.f;
     if (ok && xsl == 0) pe = nx[gr];
     if (ok && xsl == 1) pe = yv[gr];
   };
   auto xwrite = [&]() {
-    const int o = xrow * SF_XSTR + (xsl & 3) * 8 + (xsl >> 2);
-    xs[o] = px0;
-    xs[o + 4] = px1;                      // d-slot xsl + 16 -> kc + 4
+    if constexpr (G16) {
+      f16x2 vh, vl;
+      f16 h, l;
+      split_f16(px0, h, l);
+      vh[0] = h; vl[0] = l;
+      split_f16(px1, h, l);
+      vh[1] = h; vl[1] = l;
+      *(f16x2*)&xsh[xrow * SF_HSTR + xq0] = vh;
+      *(f16x2*)&xsh[xrow * SF_HSTR + SF_DMAX + xq0] = vl;
+    } else {
+      const int o = xrow * SF_XSTR + (xsl & 3) * 8 + (xsl >> 2);
+      xs[o] = px0;
+      xs[o + 4] = px1;                    // d-slot xsl + 16 -> kc + 4
+    }
     if (xsl < 2) xs[xrow * SF_XSTR + 32 + xsl] = pe;
   };
 
@@ -779,35 +848,85 @@ sf_tile(const float* __restrict__ Xs, const float* __restrict__ As,
   double kyacc[NG] = {0.0};               // DIAG only: Ky partial per group
   auto generate = [&](int kb) {
     f32x4 dacc[2][NG];
+    if constexpr (G16) {
+      // x'.a' = xh.ah + 2^-11 (xh.al + xl.ah) [+ 2^-22 xl.al, dropped]: three
+      // 16x16x32 f16 MFMAs chained on one accumulator, the smaller products
+      // first, one rescale between.  One window (two column groups, four
+      // fragments) at a time: the A' images of a window are 16 registers and
+      // the four chains cover each other's latency.
+      f16x8 xh[2], xl[2];
 #pragma unroll
-    for (int rg = 0; rg < 2; ++rg)
+      for (int rg = 0; rg < 2; ++rg) {
+        const f16* xr = &xsh[(rg * 16 + l16) * SF_HSTR + kgrp * 8];
+        xh[rg] = *(const f16x8*)xr;
+        xl[rg] = *(const f16x8*)(xr + SF_DMAX);
+      }
 #pragma unroll
-      for (int g = 0; g < NG; ++g) dacc[rg][g] = {0.f, 0.f, 0.f, 0.f};
+      for (int w = 0; w < NG / 2; ++w) {
+        f16x8 ah[2], al[2];
 #pragma unroll
-    for (int h = 0; h < 2; ++h) {         // kc = 4h .. 4h+3, in d order
-      if (h * 16 < d) {                   // uniform; skipped slots are 0*0
-        f32x4 xa[2], ab[NG];
+        for (int j = 0; j < 2; ++j) {
+          const f16* ar = &awh[(w * SY_CT + (wave * 2 + j) * 16 + l16) *
+                                   SF_HSTR + kgrp * 8];
+          ah[j] = *(const f16x8*)ar;
+          al[j] = *(const f16x8*)(ar + SF_DMAX);
+        }
+        const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int rg = 0; rg < 2; ++rg)
-          xa[rg] = *(const f32x4*)&xs[(rg * 16 + l16) * SF_XSTR + kgrp * 8 +
-                                      h * 4];
 #pragma unroll
-        for (int g = 0; g < NG; ++g)
-          ab[g] = *(const f32x4*)&aw[((g >> 1) * SY_CT +
-                                      (wave * 2 + (g & 1)) * 16 + l16) *
-                                         SF_XSTR + kgrp * 8 + h * 4];
+          for (int j = 0; j < 2; ++j)
+            dacc[rg][w * 2 + j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(
+                xh[rg], al[j], zero, 0, 0, 0);
 #pragma unroll
-        for (int u = 0; u < 4; ++u)
+        for (int rg = 0; rg < 2; ++rg)
+#pragma unroll
+          for (int j = 0; j < 2; ++j)
+            dacc[rg][w * 2 + j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(
+                xl[rg], ah[j], dacc[rg][w * 2 + j], 0, 0, 0);
+#pragma unroll
+        for (int rg = 0; rg < 2; ++rg)
+#pragma unroll
+          for (int j = 0; j < 2; ++j) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) dacc[rg][w * 2 + j][r] *= SF_LO_INV;
+            dacc[rg][w * 2 + j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(
+                xh[rg], ah[j], dacc[rg][w * 2 + j], 0, 0, 0);
+          }
+        // one window's A' images live at a time (register budget)
+        __builtin_amdgcn_sched_barrier(0);
+      }
+    } else {
+#pragma unroll
+      for (int rg = 0; rg < 2; ++rg)
+#pragma unroll
+        for (int g = 0; g < NG; ++g) dacc[rg][g] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {       // kc = 4h .. 4h+3, in d order
+        if (h * 16 < d) {                 // uniform; skipped slots are 0*0
+          f32x4 xa[2], ab[NG];
 #pragma unroll
           for (int rg = 0; rg < 2; ++rg)
+            xa[rg] = *(const f32x4*)&xs[(rg * 16 + l16) * SF_XSTR +
+                                        kgrp * 8 + h * 4];
 #pragma unroll
-            for (int g = 0; g < NG; ++g)
-              dacc[rg][g] = __builtin_amdgcn_mfma_f32_16x16x4f32(
-                  xa[rg][u], ab[g][u], dacc[rg][g], 0, 0, 0);
+          for (int g = 0; g < NG; ++g)
+            ab[g] = *(const f32x4*)&aw[((g >> 1) * SY_CT +
+                                        (wave * 2 + (g & 1)) * 16 + l16) *
+                                           SF_XSTR + kgrp * 8 + h * 4];
+#pragma unroll
+          for (int u = 0; u < 4; ++u)
+#pragma unroll
+            for (int rg = 0; rg < 2; ++rg)
+#pragma unroll
+              for (int g = 0; g < NG; ++g)
+                dacc[rg][g] = __builtin_amdgcn_mfma_f32_16x16x4f32(
+                    xa[rg][u], ab[g][u], dacc[rg][g], 0, 0, 0);
+        }
+        // keep the second half's fragment loads out of the first half's
+        // live range (register budget)
+        __builtin_amdgcn_sched_barrier(0);
       }
-      // keep the second half's fragment loads out of the first half's
-      // live range (register budget)
-      __builtin_amdgcn_sched_barrier(0);
     }
 #pragma unroll
     for (int rg = 0; rg < 2; ++rg) {
@@ -878,7 +997,13 @@ sf_tile(const float* __restrict__ Xs, const float* __restrict__ As,
     mfma_pass(ltl, DIAG ? lt : rt);       // lo * hi
   }
 
-  syrk_epilogue<true>(acc, KK, m, i0, j0, !DIAG, wr, wc, l16, kgrp);
+  // the block's tile of partial sums -> its own slot, fragment-major
+  // ([a*8 + b][thread] f32x4): every wave store is 1 KB contiguous
+#pragma unroll
+  for (int a = 0; a < 4; ++a)
+#pragma unroll
+    for (int b = 0; b < 8; ++b)
+      *(f32x4*)&part[((a * 8 + b) * SY_WG + tid) * 4] = acc[a][b];
 
   if (DIAG) {
     // the 4 k-groups of a wave hold partials of the same 16 columns
@@ -893,7 +1018,7 @@ sf_tile(const float* __restrict__ Xs, const float* __restrict__ As,
   }
 }
 
-template <int FAM>
+template <int FAM, bool G16>
 __global__ void __launch_bounds__(SY_WG, 2)
 syrk_fused_gen_kernel(const float* __restrict__ Xs,   // [c, d] pre-scaled
                       const float* __restrict__ As,   // [m, d] pre-scaled
@@ -904,7 +1029,7 @@ syrk_fused_gen_kernel(const float* __restrict__ Xs,   // [c, d] pre-scaled
                       const int c, const int m, const int d, const int ntile,
                       const int split_k,
                       double* __restrict__ Ky,        // [m] accumulated
-                      float* __restrict__ KK) {       // [m, m] accumulated
+                      float* __restrict__ partials) { // [slice][tile] tiles
   __shared__ __align__(16) bf16 lt[SY_CT * SY_STR];
   __shared__ __align__(16) bf16 rt[SY_CT * SY_STR];
   __shared__ __align__(16) bf16 ltl[SY_CT * SY_STR];
@@ -918,15 +1043,55 @@ syrk_fused_gen_kernel(const float* __restrict__ Xs,   // [c, d] pre-scaled
   const int tj = ti + rem;
   int kb0, kb1;                           // empty slice: block-uniform exit
   if (!syrk_kslice(c, split_k, blockIdx.y, kb0, kb1)) return;
+  float* part = partials + sf_partial_offset(blockIdx.y, blockIdx.x,
+                                             gridDim.x);
 
   if (ti == tj)
-    sf_tile<true, FAM>(Xs, As, nx, na, amp, yv, c, m, d, ti * SY_CT,
-                       tj * SY_CT, kb0, kb1, lt, rt, ltl, rtl, xs, aw, Ky,
-                       KK);
+    sf_tile<true, FAM, G16>(Xs, As, nx, na, amp, yv, c, m, d, ti * SY_CT,
+                            tj * SY_CT, kb0, kb1, lt, rt, ltl, rtl, xs, aw,
+                            Ky, part);
   else
-    sf_tile<false, FAM>(Xs, As, nx, na, amp, yv, c, m, d, ti * SY_CT,
-                        tj * SY_CT, kb0, kb1, lt, rt, ltl, rtl, xs, aw, Ky,
-                        KK);
+    sf_tile<false, FAM, G16>(Xs, As, nx, na, amp, yv, c, m, d, ti * SY_CT,
+                             tj * SY_CT, kb0, kb1, lt, rt, ltl, rtl, xs, aw,
+                             Ky, part);
+}
+
+// KK += the k-slices' partial tiles of syrk_fused_gen_kernel, summed per
+// element in ascending slice order; an off-diagonal tile's element and its
+// mirror receive the same sum.  Grid (tiles, 32 fragments), SY_WG threads:
+// thread t of block (tile, f) owns the f32x4 that thread t of the tile's
+// blocks stored for fragment f, i.e. 4 consecutive rows of one column, so
+// each KK element has one owner and is accumulated plainly.  Slices without
+// rows wrote nothing and are not read: they are the trailing ones of
+// syrk_kslice.
+__global__ void __launch_bounds__(SY_WG)
+syrk_fused_reduce_kernel(const float* __restrict__ partials,
+                         const int c, const int m, const int ntile,
+                         const int split_k,
+                         float* __restrict__ KK) {      // [m, m] accumulated
+  int ti = 0, rem = blockIdx.x;
+  while (rem >= ntile - ti) { rem -= ntile - ti; ++ti; }
+  const int tj = ti + rem;
+  const int frag = blockIdx.y, a = frag >> 3, b = frag & 7;
+  const SyLane L = sy_lane();
+
+  f32x4 sum = {0.f, 0.f, 0.f, 0.f};
+  for (int s = 0; s < split_k; ++s) {
+    int kb0, kb1;
+    if (!syrk_kslice(c, split_k, s, kb0, kb1)) break;
+    sum += *(const f32x4*)&partials[sf_partial_offset(s, blockIdx.x,
+                                                      gridDim.x) +
+                                    (frag * SY_WG + L.tid) * 4];
+  }
+  const int gj = tj * SY_CT + L.wc + b * 16 + L.l16;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int gi = ti * SY_CT + L.wr + a * 16 + L.kgrp * 4 + r;
+    if (gi < m && gj < m) {
+      KK[(size_t)gi * m + gj] += sum[r];
+      if (ti != tj) KK[(size_t)gj * m + gi] += sum[r];
+    }
+  }
 }
 
 // ---------------------------------------------------------------------------
@@ -1026,11 +1191,12 @@ colsum_gemv_kernel(const bf16* __restrict__ Kc,   // [c, m]
 // ---------------------------------------------------------------------------
 // launchers
 // ---------------------------------------------------------------------------
-// KERNEL<family>, or null for an unknown family code
-#define FAMILY_KERNEL(KERNEL, family)                       \
-  ((family) == GEOM_FAM_RBF   ? KERNEL<GEOM_FAM_RBF>        \
-   : (family) == GEOM_FAM_M32 ? KERNEL<GEOM_FAM_M32>        \
-   : (family) == GEOM_FAM_M52 ? KERNEL<GEOM_FAM_M52>        \
+// KERNEL<family[, further template arguments]>, or null for an unknown
+// family code
+#define FAMILY_KERNEL(KERNEL, family, ...)                            \
+  ((family) == GEOM_FAM_RBF   ? KERNEL<GEOM_FAM_RBF, ##__VA_ARGS__>   \
+   : (family) == GEOM_FAM_M32 ? KERNEL<GEOM_FAM_M32, ##__VA_ARGS__>   \
+   : (family) == GEOM_FAM_M52 ? KERNEL<GEOM_FAM_M52, ##__VA_ARGS__>   \
                               : nullptr)
 
 extern "C" hipError_t launch_cross_kernel_tile(
@@ -1103,14 +1269,20 @@ extern "C" hipError_t launch_syrk_bf16(const void* KcT, const void* KlT,
 extern "C" hipError_t launch_syrk_fused_gen(
     const float* Xs, const float* As, const float* nx, const float* na,
     float amp, const float* yv, int c, int m, int d, int split_k,
-    double* Ky, float* KK, int family, hipStream_t stream) {
-  const auto kern = FAMILY_KERNEL(syrk_fused_gen_kernel, family);
+    double* Ky, float* KK, float* partials, int family, int gen_f16,
+    hipStream_t stream) {
+  const auto kern =
+      gen_f16 ? FAMILY_KERNEL(syrk_fused_gen_kernel, family, true)
+              : FAMILY_KERNEL(syrk_fused_gen_kernel, family, false);
   if (!kern) return hipErrorInvalidValue;
   const int ntile = (m + SY_CT - 1) / SY_CT;
   dim3 grid(ntile * (ntile + 1) / 2, split_k);   // upper-triangle tiles
   hipLaunchKernelGGL(kern, grid, dim3(SY_WG), 0, stream,
                      Xs, As, nx, na, amp, yv, c, m, d, ntile, split_k, Ky,
-                     KK);
+                     partials);
+  // same stream: runs after every block's partial tile is written
+  hipLaunchKernelGGL(syrk_fused_reduce_kernel, dim3(grid.x, 32), dim3(SY_WG),
+                     0, stream, partials, c, m, ntile, split_k, KK);
   return hipGetLastError();
 }
 

@@ -195,6 +195,28 @@ static GEOM_HD inline bool ppa_predict_supported_md(long m, long d) {
 #define SY_CT 256     // output tile edge (per block)
 #define SY_BK 32      // k rows per staged block
 #define SF_DMAX 32    // syrk_fused_gen: d-slots per row that fit its LDS
+// syrk_fused_gen's f16 generator takes scaled coordinates below this bound
+// (half the f16 range, 65504); above it the fp32 generator runs
+#define SF_F16_ABS_LIMIT 32768.0
+
+// syrk_fused_gen's partial tiles: one SY_CT x SY_CT fp32 tile per (k-slice
+// with rows, upper-triangle tile), slice-major
+static GEOM_HD inline size_t sf_partial_offset(int slice, int tile,
+                                               int tiles) {
+  return ((size_t)slice * tiles + tile) * (SY_CT * SY_CT);
+}
+
+// floats of that buffer for a chunk of c rows: the slices with rows are the
+// first ceil(kblocks / per) of split_k, per = ceil(kblocks / split_k)
+static GEOM_HD inline size_t sf_partial_floats(long c, long m, long split_k) {
+  const long kblocks = (c + SY_BK - 1) / SY_BK;
+  if (kblocks < 1 || split_k < 1) return 0;
+  const long per = (kblocks + split_k - 1) / split_k;
+  const long ntile = (m + SY_CT - 1) / SY_CT;
+  return sf_partial_offset((int)((kblocks + per - 1) / per), 0,
+                           (int)(ntile * (ntile + 1) / 2));
+}
+
 // largest lower-triangle tile set the split-k family (syrk_bf16,
 // syrk_fused_gen) takes; larger sets go to the k-synchronized kernel
 #define SY_SPLITK_MAX_TILES 256

@@ -61,7 +61,8 @@ hipError_t launch_syrk_bf16_sync(const void* KcT, const void* KlT, int c,
 hipError_t launch_syrk_fused_gen(
     const float* Xs, const float* As, const float* nx, const float* na,
     float amp, const float* yv, int c, int m, int d, int split_k,
-    double* Ky, float* KK, int family, hipStream_t stream);
+    double* Ky, float* KK, float* partials, int family, int gen_f16,
+    hipStream_t stream);   // partials: sf_partial_floats(c, m, split_k)
 
 hipError_t launch_colsum_gemv(const void* Kc, const float* y, int c, int m,
                               double* Ky, hipStream_t stream);

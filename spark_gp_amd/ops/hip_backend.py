@@ -236,6 +236,19 @@ def kmn_knm_and_kmny(kernel: Kernel, active: torch.Tensor,
         svec = _scale_vector(cs, theta, d, X.device)
         As = (act32 * svec).contiguous()
         na = (As * As).sum(-1).contiguous()
+    if plan.generator == "fused" and n > 0:
+        # the f16 generator needs the scaled coordinates inside its range:
+        # bound them once for all chunks (one pass over X, one host read)
+        xlo, xhi = torch.aminmax(X)
+        alo, ahi = torch.aminmax(As)
+        absmax = float(torch.maximum(
+            torch.maximum(-xlo, xhi) * svec.abs().max(),
+            torch.maximum(-alo, ahi)))
+        gen = ppa_plan.ppa_fused_gen(absmax)
+        # scratch of the k-slices' partial tiles, shared by all chunks
+        partials = torch.empty(
+            ppa_plan.ppa_fused_partials_numel(m, plan.split_k),
+            dtype=torch.float32, device=X.device)
     if plan.syrk == "sync":
         sync_tiles = _syrk_sync_tiles(m, X.device)
     for s in range(0, n, plan.chunk_rows):
@@ -248,7 +261,8 @@ def kmn_knm_and_kmny(kernel: Kernel, active: torch.Tensor,
             nx = (Xs * Xs).sum(-1).contiguous()
         if plan.generator == "fused":
             ext.ppa_fused_acc(Xs, As, nx, na, C, yc, Ky, KK, plan.split_k,
-                              family=fam)
+                              family=fam, gen=gen, absmax=absmax,
+                              partials=partials)
             continue
         if plan.generator == "mfma":
             KcT, KlT = ext.cross_mfma_ppa(Xs, As, nx, na, C, yc, Ky,

@@ -21,9 +21,18 @@ SYRK_TILE = 256
 # Largest feature dimension the fused kernel takes (SF_DMAX): the fp32 A'
 # windows of one tile (2 x 256 x 36 floats) share the 160 KB LDS with the
 # four bf16 operand tiles, which leaves room for 32 d-slots per row.
-# Generation cost also grows as 512*d/32 f32 MFMAs per k-step, paid by every
-# tile that uses a window, so larger d stays on the staged two-kernel path.
+# Generation costs 192 f16 MFMAs (16x16x32: its K extent is the 32 d-slots) per
+# k-step of an off-diagonal tile, next to the 768 bf16 MFMAs of the products;
+# the fp32 generator it replaces by default costs 512*d/32 f32 MFMAs at twice
+# the cycles each.  Either is paid by every tile that uses a window, and a
+# larger d needs a second K pass and more LDS, so it stays on the staged
+# two-kernel path.
 FUSED_MAX_D = 32
+
+# The fused kernel's f16 generator splits every scaled coordinate into two
+# f16 terms, which overflow at 65504: it takes coordinates below this bound
+# (SF_F16_ABS_LIMIT) and the fp32 generator takes the rest.
+FUSED_F16_ABS_LIMIT = 32768.0
 
 # The split-k SYRK family owns tile sets up to 256 (m <= 5632,
 # SY_SPLITK_MAX_TILES); larger ones go to the k-synchronized kernel, which
@@ -33,7 +42,8 @@ FUSED_MAX_TILES = 256
 # The caller's chunk_rows bounds the staged path's two [m, chunk] bf16
 # buffers (4*m bytes per row).  The fused path's only temporary is the
 # scaled X chunk (4*d bytes per row), and every k-slice ends in a full tile
-# of fp32 atomics, so longer chunks are cheaper — but they lengthen the fp32
+# stored and reduced (fp32 atomics when this was measured), so longer chunks
+# are cheaper — but they lengthen the fp32
 # register accumulation.  Measured (PROFILES.md, round 3): 1x/2x/4x give
 # 83.6/77.4/74.7 ms for the 10M-row stage; KK error against the fp64
 # branch at 2M rows is 1.00/1.11/1.31 x the two-kernel path's, and the
@@ -83,11 +93,32 @@ def ppa_fused_gate(m: int, d: int, dtype) -> bool:
     return syrk_tile_count(m) <= FUSED_MAX_TILES
 
 
+def ppa_fused_gen(absmax: float) -> str:
+    """Generator of the fused kernel, ``"f16"`` or ``"f32"``, for scaled
+    coordinates bounded by ``absmax`` (of X' and A' together).  The f16
+    generator runs inside its range; a NaN bound is outside it.
+    ``SPARK_GP_AMD_PPA_GEN=f32`` selects the fp32 generator (A/B)."""
+    switch = os.environ.get("SPARK_GP_AMD_PPA_GEN", "auto")
+    if switch not in ("auto", "f32"):
+        raise ValueError("SPARK_GP_AMD_PPA_GEN must be 'auto' or 'f32', got "
+                         f"{switch!r}")
+    if switch == "f32":
+        return "f32"
+    return "f16" if absmax < FUSED_F16_ABS_LIMIT else "f32"
+
+
 def ppa_fused_split_k(m: int) -> int:
     """k-slices per chunk: with no operand windows to keep cache-resident,
     the only concern is filling the 256 CUs once with whole blocks (capped:
-    every slice ends in a full tile of fp32 atomics)."""
+    every slice ends in a full partial tile, stored and reduced)."""
     return max(1, min(64, 256 // syrk_tile_count(m)))
+
+
+def ppa_fused_partials_numel(m: int, split_k: int) -> int:
+    """fp32 elements of the fused kernel's partial-tile buffer for any chunk
+    length: one tile per (k-slice, output tile).  With the plan's split_k =
+    256 // tiles that is at most 256 tiles of 256 KB, 64 MB."""
+    return split_k * syrk_tile_count(m) * SYRK_TILE * SYRK_TILE
 
 
 def syrk_staged_split_k(m: int) -> int:
