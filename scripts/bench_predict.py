@@ -1,7 +1,7 @@
 """Prediction microbenchmark: the staged path against the fused kernel.
 
 Usage (GPU box):  python scripts/bench_predict.py [--shapes T,M,D ...]
-                      [--rounds R] [--budget-gb G] [--out FILE]
+                      [--rounds R] [--budget-gb G] [--out FILE] [--wide]
 
 For every shape, family (RBF, Matern 5/2) and mode (mean only, mean and
 variance) it times, alternating and after a warm-up of each,
@@ -16,6 +16,11 @@ and reports per path the best and worst wall time of the rounds (host clock
 around a device synchronise), the peak device memory above the inputs, the
 row-tile height the gate chose, and the largest difference between the two
 results.  One JSON line per (shape, family, mode).
+
+With --wide it times, with variance, what ``stream=True`` runs at the shape
+(the fused kernel where its gate takes m, else the chunked staged path at the
+default chunk_rows) against ``hip_backend.predict_wide`` (predict_wide.hip),
+the kernel behind ``stream="wide"``, in the same alternating way.
 """
 import argparse
 import json
@@ -114,12 +119,53 @@ def bench(t, m, d, family, with_var, rounds, budget_gb, dev):
     }
 
 
+def bench_wide(t, m, d, family, rounds, dev):
+    g = torch.Generator().manual_seed(t + m + d)
+    X = torch.rand(t, d, generator=g).to(dev)
+    A = torch.rand(m, d, generator=g).to(dev)
+    M = torch.randn(m, m, generator=g, dtype=torch.float64)
+    M = (0.5 * (M + M.T) / m).to(dev)
+    mv = torch.randn(m, generator=g, dtype=torch.float64).to(dev)
+    kernel = make_kernel(family, d)
+    raw = GaussianProjectedProcessRawPredictor(mv, M, kernel, A)
+    if not hip_backend.supports_predict_wide(kernel, X, m):
+        raise SystemExit(f"the wide gate refuses (m, d) = ({m}, {d})")
+
+    def stream():
+        return raw.predict(X, stream=True)
+
+    def wide():
+        return hip_backend.predict_wide(kernel, X, A, mv, M, True)
+
+    peak_s, (mean_s, var_s) = peak_above(stream)      # also the warm-up
+    peak_w, (mean_w, var_w) = peak_above(wide)
+    diff = {"mean": float((mean_w - mean_s).abs().max()),
+            "var": float((var_w - var_s).abs().max()),
+            "var_scale": float(var_s.abs().max())}
+    del mean_s, var_s, mean_w, var_w
+    ts, tw = [], []
+    for _ in range(rounds):                           # alternate
+        ts.append(timed(stream)[0])
+        tw.append(timed(wide)[0])
+    narrow = hip_backend.supports_predict(kernel, X, m)
+    return {
+        "t": t, "m": m, "d": d, "family": family, "with_var": True,
+        "stream_path": "fused" if narrow else "chunked",
+        "stream_ms": [min(ts), max(ts)], "wide_ms": [min(tw), max(tw)],
+        "speedup_best": min(ts) / min(tw),
+        "stream_peak_bytes": peak_s, "wide_peak_bytes": peak_w,
+        "max_abs_diff": diff,
+    }
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--shapes", nargs="*", default=DEFAULT_SHAPES)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--budget-gb", type=float, default=8.0)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--wide", action="store_true",
+                    help="stream=True against the wide fused kernel")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "bench_predict.py needs a GPU"
     dev = torch.device("cuda:0")
@@ -127,9 +173,11 @@ def main():
     for shape in args.shapes:
         t, m, d = (int(v) for v in shape.split(","))
         for family in ("rbf", "m52"):
-            for with_var in (False, True):
-                res = bench(t, m, d, family, with_var, args.rounds,
-                            args.budget_gb, dev)
+            for with_var in ((True,) if args.wide else (False, True)):
+                res = (bench_wide(t, m, d, family, args.rounds, dev)
+                       if args.wide else
+                       bench(t, m, d, family, with_var, args.rounds,
+                             args.budget_gb, dev))
                 lines.append(json.dumps(res))
                 print(lines[-1], flush=True)
                 if args.out:

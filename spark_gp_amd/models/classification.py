@@ -115,7 +115,7 @@ class GaussianProcessClassificationModel:
         from scipy.special import ndtr
         return ndtr(z)
 
-    def _latent(self, X, stream: bool = False, chunk_rows: int = 262144
+    def _latent(self, X, stream=False, chunk_rows: int = 262144
                 ) -> Tuple[torch.Tensor, torch.Tensor]:
         """Latent (mean, var); ``stream=True`` bounds peak memory for any
         number of rows (the raw predictor's ``predict``)."""
@@ -124,11 +124,11 @@ class GaussianProcessClassificationModel:
         if Xt.dim() == 1:
             Xt = Xt.unsqueeze(0)
         if stream:
-            return self.raw.predict(Xt, with_var=True, stream=True,
+            return self.raw.predict(Xt, with_var=True, stream=stream,
                                     chunk_rows=chunk_rows)
         return self.raw.predict(Xt, with_var=True)
 
-    def predict_raw(self, X, stream: bool = False,
+    def predict_raw(self, X, stream=False,
                     chunk_rows: int = 262144) -> np.ndarray:
         """(-f, f) scores per row (``GaussianProcessClassifier.scala:153-156``)."""
         f, _ = self._latent(X, stream, chunk_rows)
@@ -136,7 +136,7 @@ class GaussianProcessClassificationModel:
         return np.stack([-f, f], axis=-1)
 
     def predict_proba(self, X, averaged: bool = False,
-                      quadrature_points: int = 32, stream: bool = False,
+                      quadrature_points: int = 32, stream=False,
                       chunk_rows: int = 262144) -> np.ndarray:
         """[p(y=0), p(y=1)] per row.
 
@@ -156,7 +156,7 @@ class GaussianProcessClassificationModel:
             p1 = self._squash(f).cpu().numpy()
         return np.stack([1.0 - p1, p1], axis=-1)
 
-    def predict(self, X, stream: bool = False,
+    def predict(self, X, stream=False,
                 chunk_rows: int = 262144) -> np.ndarray:
         f, _ = self._latent(X, stream, chunk_rows)
         return (f.cpu().numpy() > 0).astype(np.float64)

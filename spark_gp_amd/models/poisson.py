@@ -88,7 +88,7 @@ class GaussianProcessPoissonModel:
         self.raw = raw
         self._instr: Optional[Instrumentation] = None
 
-    def _latent(self, X, stream: bool = False, chunk_rows: int = 262144
+    def _latent(self, X, stream=False, chunk_rows: int = 262144
                 ) -> Tuple[torch.Tensor, torch.Tensor]:
         """Latent (mean, var); ``stream=True`` bounds peak memory for any
         number of rows (the raw predictor's ``predict``)."""
@@ -97,11 +97,11 @@ class GaussianProcessPoissonModel:
         if Xt.dim() == 1:
             Xt = Xt.unsqueeze(0)
         if stream:
-            return self.raw.predict(Xt, with_var=True, stream=True,
+            return self.raw.predict(Xt, with_var=True, stream=stream,
                                     chunk_rows=chunk_rows)
         return self.raw.predict(Xt, with_var=True)
 
-    def predict(self, X, return_std: bool = False, stream: bool = False,
+    def predict(self, X, return_std: bool = False, stream=False,
                 chunk_rows: int = 262144):
         """Posterior-expected count rate E[exp(f*)] = exp(mu + var/2).
 
@@ -118,7 +118,7 @@ class GaussianProcessPoissonModel:
         std = torch.sqrt(rate + var_lam)
         return rate.cpu().numpy(), std.cpu().numpy()
 
-    def predict_latent(self, X, stream: bool = False,
+    def predict_latent(self, X, stream=False,
                        chunk_rows: int = 262144):
         """(mean, var) of the latent log-rate."""
         mu, var = self._latent(X, stream, chunk_rows)

@@ -153,17 +153,27 @@ def cross_kernel(kernel: Kernel, Xtest: torch.Tensor, Xtrain: torch.Tensor):
 
 def predict_stream(kernel: Kernel, X: torch.Tensor, active: torch.Tensor,
                    mv: torch.Tensor, M: torch.Tensor, with_var: bool = True,
-                   chunk_rows: int = 262144):
+                   chunk_rows: int = 262144, stream=True):
     """PPA mean [t] and (``with_var``) variance [t] in fp64 with peak memory
     bounded independently of t: the fused HIP kernel (no [t, m] array at
     all) where its gate takes the kernel tree and (m, d); otherwise the
     staged cross-kernel / GEMV / quadratic form over row chunks of
-    ``chunk_rows`` — any tree, any m, and on CPU."""
+    ``chunk_rows`` — any tree, any m, and on CPU.
+
+    ``stream="wide"`` (as the predict methods take it) puts the wide fused
+    kernel between the two: where the first gate refuses and its own takes
+    the call (m up to 8192), one launch with a scratch of
+    min(ceil(t / 128), compute units) x 128 x m floats."""
+    if isinstance(stream, str) and stream != "wide":
+        raise ValueError(f"stream must be a bool or 'wide', got {stream!r}")
     cs = compile_kernel(kernel)
     hip = (_backend_for("predict_stream", X)
            if cs is not None and cs.base in BASES else None)
     if hip is not None and hip.supports_predict(kernel, X, active.shape[0]):
         return hip.predict(kernel, X, active, mv, M, with_var)
+    if (stream == "wide" and hip is not None
+            and hip.supports_predict_wide(kernel, X, active.shape[0])):
+        return hip.predict_wide(kernel, X, active, mv, M, with_var)
     if chunk_rows < 1:
         raise ValueError(f"chunk_rows must be >= 1, got {chunk_rows}")
     t = X.shape[0]

@@ -512,6 +512,57 @@ std::tuple<torch::Tensor, c10::optional<torch::Tensor>> ppa_predict(
   return {mean, var};
 }
 
+// K14, wide form (predict_wide.hip): the same outputs for 1 <= m <=
+// PPW_M_MAX.  Persistent blocks over 128-row tiles keep the cross rows in a
+// scratch buffer of grid x 128 x mp floats, allocated here: bounded by the
+// grid (one block per compute unit; max_blocks > 0 caps it), never by t.
+bool ppa_predict_wide_supported(int64_t m, int64_t d) {
+  return ppa_predict_wide_supported_md((long)m, (long)d);
+}
+
+std::tuple<torch::Tensor, c10::optional<torch::Tensor>> ppa_predict_wide(
+    torch::Tensor X, torch::Tensor A, torch::Tensor s2, double amp,
+    torch::Tensor mv, torch::Tensor M, double kxx, bool want_var,
+    int64_t family, int64_t max_blocks) {
+  check_family(family);
+  check_arg(X, "X", F32, {ANY, ANY});
+  const int64_t t = X.size(0), d = X.size(1);
+  check_arg(A, "A", F32, {ANY, d});
+  const int64_t m = A.size(0);
+  check_vec(s2, "s2", F32, d);
+  check_arg(mv, "mv", F64, {m});
+  check_arg(M, "M", F64, {m, m});
+  TORCH_CHECK(ppa_predict_wide_supported(m, d), "A: unsupported (m, d) = (",
+              m, ", ", d,
+              ") for ppa_predict_wide; query ppa_predict_wide_supported");
+  TORCH_CHECK(max_blocks >= 0, "max_blocks must be >= 0 (0: no cap), got ",
+              max_blocks);
+  check_same_gpu({{&X, "X"}, {&A, "A"}, {&s2, "s2"}, {&mv, "mv"}, {&M, "M"}});
+  make_contiguous({&X, &A, &s2, &mv, &M});
+  auto mean = torch::empty({t}, like(X, F64));
+  c10::optional<torch::Tensor> var;
+  if (want_var) var = torch::empty({t}, like(X, F64));
+  int cus = 0;
+  check_hip(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount,
+                                  X.get_device()),
+            "ppa_predict_wide: compute unit count");
+  const long grid = ppw_grid((long)t, cus, (long)max_blocks);
+  torch::Tensor scratch;
+  if (want_var)
+    scratch = torch::empty({(int64_t)ppw_scratch_floats(grid, (int)m)},
+                           like(X, F32));
+  check_hip(launch_ppa_predict_wide(
+                X.data_ptr<float>(), A.data_ptr<float>(),
+                s2.data_ptr<float>(), (float)amp, mv.data_ptr<double>(),
+                M.data_ptr<double>(), kxx, (long)t, (int)m, (int)d,
+                want_var ? scratch.data_ptr<float>() : nullptr, (int)grid,
+                mean.data_ptr<double>(),
+                want_var ? var->data_ptr<double>() : nullptr, (int)family,
+                current_stream()),
+            "ppa_predict_wide");
+  return {mean, var};
+}
+
 // ---------------------------------------------------------------------------
 // K13: blocked fp64 Cholesky path (big_chol.hip) — host orchestration
 // ---------------------------------------------------------------------------
@@ -707,6 +758,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("ppa_predict_supported", &ppa_predict_supported);
   mod.def("ppa_predict_tile_rows", &ppa_predict_tile_rows,
           "test rows per block of ppa_predict at m active points (0: none)");
+  mod.def("ppa_predict_wide", &ppa_predict_wide,
+          "K14 for m up to 8192: persistent 128-row tiles, cross rows in a "
+          "grid-bounded scratch, M panels shared through LDS (CDNA4)",
+          pybind11::arg("X"), pybind11::arg("A"), pybind11::arg("s2"),
+          pybind11::arg("amp"), pybind11::arg("mv"), pybind11::arg("M"),
+          pybind11::arg("kxx"), pybind11::arg("want_var"),
+          pybind11::arg("family") = (int)GEOM_FAM_RBF,
+          pybind11::arg("max_blocks") = 0);
+  mod.def("ppa_predict_wide_supported", &ppa_predict_wide_supported);
   mod.def("syrk_bf16_sync_acc", &syrk_bf16_sync_acc,
           "k-synchronized persistent SYRK for large m (CDNA4)");
   mod.def("syrk_bf16_acc", &syrk_bf16_acc,

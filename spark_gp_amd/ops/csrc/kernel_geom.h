@@ -1,6 +1,7 @@
 // Kernel geometry shared by the device code and the host-side gates: the
 // LDS budgets of the fused expert kernels and the SYRK tile constants.
-// Included by expert_nll.hip, laplace.hip, cross_syrk.hip, predict.hip (hipcc) and by
+// Included by expert_nll.hip, laplace.hip, cross_syrk.hip, predict.hip,
+// predict_wide.hip (hipcc) and by
 // bindings.cpp (host compiler), so a *_supported() answer and the launch it
 // guards are computed by the same function.
 #pragma once
@@ -191,8 +192,58 @@ static GEOM_HD inline bool ppa_predict_supported_md(long m, long d) {
   return d >= 1 && d <= 65536 && pp_tile_rows(m) != 0;
 }
 
+// ---- wide fused prediction (predict_wide.hip) -----------------------------
+// For active sets past the narrow kernel's LDS plan: persistent blocks take
+// row tiles of PPW_R rows, a tile's fp32 cross rows c[PPW_R][mp] live in the
+// block's slab of a global scratch buffer [grid, PPW_R, mp], and LDS holds
+// the double-buffered PPW_P x PPW_W panels of M that the block's waves share.
+#define PPW_R 128        // rows per tile: a 16-row MFMA slab per wave
+#define PPW_P 64         // k depth of a staged M panel (4 k blocks of 16)
+#define PPW_W 64         // its columns: 4 MFMA column tiles per wave
+// panel row stride in doubles, = 4 (mod 8): the B-fragment read
+// Ms[4 (l>>4) + s][16 b + (l&15)] of a wave is 4 rows of 16 contiguous
+// doubles; rows 4 apart then start 32 words apart modulo 64, so the two rows
+// of a 32-lane group fall on disjoint halves of 64 banks
+#define PPW_MSTR (PPW_W + 4)
+#define PPW_M_MAX 8192
+static_assert(PPW_R == 16 * (PP_THREADS / 64), "a 16-row slab per wave");
+static_assert(PPW_P == PPW_W, "a column panel's first k panel is its diagonal");
+static_assert(PPW_P * PPW_W % PP_THREADS == 0, "panel staged in whole passes");
+
+// LDS bytes of ppa_predict_wide_kernel; region order is its carve.  No term
+// depends on m or d.
+static GEOM_HD inline size_t ppw_lds_bytes() {
+  size_t off = 0;
+  off += a16(sizeof(double) * 2 * PPW_P * PPW_MSTR);              // M panels
+  off += a16(sizeof(float) * PP_CB * (PP_DBLK + 1));              // as
+  off += a16(sizeof(float) * PPW_R * (PP_DBLK + 1));              // xs
+  off += a16(sizeof(float) * PP_DBLK);                            // s2
+  return off;
+}
+
+static GEOM_HD inline bool ppa_predict_wide_supported_md(long m, long d) {
+  return d >= 1 && d <= 65536 && m >= 1 && m <= PPW_M_MAX &&
+         ppw_lds_bytes() <= GEOM_LDS_MAX;
+}
+
+// blocks of one launch over t rows on a device of `cus` compute units (one
+// block per unit: its LDS plan and 512 threads leave room for no second);
+// max_blocks > 0 caps it.  0 for t = 0.
+static GEOM_HD inline long ppw_grid(long t, long cus, long max_blocks) {
+  long g = (t + PPW_R - 1) / PPW_R;
+  if (g > cus) g = cus;
+  if (max_blocks > 0 && g > max_blocks) g = max_blocks;
+  return g;
+}
+
+// floats of the scratch buffer of a launch of `grid` blocks: bounded by the
+// grid, never by t
+static GEOM_HD inline size_t ppw_scratch_floats(long grid, int m) {
+  return (size_t)grid * PPW_R * (size_t)pp_mp(m);
+}
+
 // ---- SYRK kernels (cross_syrk.hip) ----------------------------------------
-#define SY_CT 256     // output tile edge (per block)
+#define SY_CT 256    // output tile edge (per block)
 #define SY_BK 32      // k rows per staged block
 #define SF_DMAX 32    // syrk_fused_gen: d-slots per row that fit its LDS
 // syrk_fused_gen's f16 generator takes scaled coordinates below this bound

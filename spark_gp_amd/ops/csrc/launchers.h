@@ -74,6 +74,15 @@ hipError_t launch_ppa_predict(
     const double* mv, const double* M, double kxx, long t, int m, int d,
     double* mean, double* var, int family, hipStream_t stream);
 
+// ---- predict_wide.hip -----------------------------------------------------
+// scratch: ppw_scratch_floats(grid, m) floats, grid <= ceil(t / PPW_R)
+// blocks; var == nullptr: mean only (M and scratch are then not touched)
+hipError_t launch_ppa_predict_wide(
+    const float* X, const float* A, const float* s2v, float amp,
+    const double* mv, const double* M, double kxx, long t, int m, int d,
+    float* scratch, int grid, double* mean, double* var, int family,
+    hipStream_t stream);
+
 // ---- big_chol.hip ---------------------------------------------------------
 hipError_t launch_dpotrf_diag(double* A, long m, int jb, double* Vout,
                               int* bad, hipStream_t stream);

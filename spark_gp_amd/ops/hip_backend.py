@@ -356,32 +356,63 @@ def magic_vector_matrix(kernel: Kernel, KK: torch.Tensor, Ky: torch.Tensor,
     return mv, PDinv * nu - Kmminv
 
 
-def supports_predict(kernel: Kernel, X: torch.Tensor, m: int) -> bool:
-    """A canonical tree on [t, d] fp32 rows whose (m, d) the fused predict
-    kernel's LDS plan takes (``ext.ppa_predict_supported``)."""
+def _supports_predict(gate, kernel: Kernel, X: torch.Tensor, m: int) -> bool:
+    """A canonical tree on [t, d] fp32 rows whose (m, d) ``gate`` (an
+    ``ext.ppa_predict*_supported``) takes."""
     cs = compile_kernel(kernel)
     if cs is None or cs.base not in BASES:
         return False
     if X.dtype != torch.float32 or X.dim() != 2:
         return False
-    return bool(ext.ppa_predict_supported(int(m), int(X.shape[1])))
+    return bool(gate(int(m), int(X.shape[1])))
 
 
-def predict(kernel: Kernel, X: torch.Tensor, active: torch.Tensor,
-            mv: torch.Tensor, M: torch.Tensor, with_var: bool = True):
-    """K14 in one launch (predict.hip): mean [t] and, with ``with_var``,
-    var [t] in fp64, with no [t, m] array in memory."""
+def _predict_args(kernel: Kernel, X: torch.Tensor, active: torch.Tensor,
+                  mv: torch.Tensor, M: torch.Tensor):
+    """(X, A, s2, amp, mv, M, kxx) and the family code, as both fused
+    predict bindings take them."""
     cs = compile_kernel(kernel)
     theta = kernel.get_hyperparameters()
     d = X.shape[-1]
     s2 = _s2_vector(cs, theta, d, X.device)
     # k(x, x) of a canonical tree is the same for every row: amp + noise
     kxx = float(kernel.self_kernel(torch.zeros(1, d, dtype=torch.float64))[0])
-    mean, var = ext.ppa_predict(
-        X, active.to(X.device, torch.float32), s2, float(cs.amp(theta)),
-        mv.to(X.device, torch.float64), M.to(X.device, torch.float64), kxx,
-        bool(with_var),
-        family=base_family(cs.base))
+    return (X, active.to(X.device, torch.float32), s2, float(cs.amp(theta)),
+            mv.to(X.device, torch.float64), M.to(X.device, torch.float64),
+            kxx), base_family(cs.base)
+
+
+def supports_predict(kernel: Kernel, X: torch.Tensor, m: int) -> bool:
+    """The fused predict kernel's LDS plan takes (m, d)
+    (``ext.ppa_predict_supported``)."""
+    return _supports_predict(ext.ppa_predict_supported, kernel, X, m)
+
+
+def predict(kernel: Kernel, X: torch.Tensor, active: torch.Tensor,
+            mv: torch.Tensor, M: torch.Tensor, with_var: bool = True):
+    """K14 in one launch (predict.hip): mean [t] and, with ``with_var``,
+    var [t] in fp64, with no [t, m] array in memory."""
+    args, fam = _predict_args(kernel, X, active, mv, M)
+    mean, var = ext.ppa_predict(*args, bool(with_var), family=fam)
+    return mean, var
+
+
+def supports_predict_wide(kernel: Kernel, X: torch.Tensor, m: int) -> bool:
+    """The wide predict kernel takes (m, d): m up to 8192
+    (``ext.ppa_predict_wide_supported``)."""
+    return _supports_predict(ext.ppa_predict_wide_supported, kernel, X, m)
+
+
+def predict_wide(kernel: Kernel, X: torch.Tensor, active: torch.Tensor,
+                 mv: torch.Tensor, M: torch.Tensor, with_var: bool = True,
+                 max_blocks: int = 0):
+    """K14 in one launch for large active sets (predict_wide.hip): the
+    outputs of ``predict``.  With ``with_var`` the binding allocates a
+    scratch of grid x 128 x (m up to 16) floats, grid = min(ceil(t / 128),
+    compute units, ``max_blocks`` if > 0): bounded independently of t."""
+    args, fam = _predict_args(kernel, X, active, mv, M)
+    mean, var = ext.ppa_predict_wide(*args, bool(with_var), family=fam,
+                                     max_blocks=int(max_blocks))
     return mean, var
 
 
