@@ -80,9 +80,43 @@ class GreedilyOptimizingActiveSetProvider(ActiveSetProvider):
 
     with p_i = c^T K_mm^-1 c, q_i = c^T PD^-1 c, mu_i = c^T magicVector and
     c the candidate's cross-kernel column; NaN-filtered distributed argmax
-    (C6/C7 collectives) picks the next inducing point."""
+    (C6/C7 collectives) picks the next inducing point.
+
+    ``incremental=True`` keeps p, q and mu up to date instead of recomputing
+    them: two Cholesky factors grow by one row per round and every candidate
+    is updated from one new cross-kernel column (``ops.greedy_state``; the
+    fused HIP kernels on GPU).  O(n mc) work and an allreduce of mc + 2
+    doubles per round instead of O(n mc^2) and mc (mc + 1), for the same
+    selection; the state takes 12 n m bytes on GPU, 16 n m on CPU."""
+
+    def __init__(self, incremental: bool = False):
+        self.incremental = bool(incremental)
+
+    def _select_incremental(self, m, X, y, kernel, seed, comm):
+        from . import ops
+        active = comm.sample_rows(X, 1, seed)           # 1 random start
+        if m <= 1:
+            return active
+        state = ops.greedy_state(kernel, X, y, m - 1)
+        state.append(active[0], comm)
+        while True:
+            best_local, best_val = state.best()
+            # distributed argmax: max value, then lowest owning rank wins
+            gmax = comm.allreduce_scalar(best_val, op="max")
+            my = comm.rank if (best_val == gmax) else 1 << 30
+            winner = int(comm.allreduce_scalar(float(my), op="min"))
+            row = torch.zeros(1, X.shape[1], dtype=X.dtype, device=X.device)
+            if comm.rank == winner:
+                row[0] = X[best_local]
+            comm.allreduce_(row)
+            active = torch.cat([active, row], dim=0)
+            if active.shape[0] >= m:
+                return active
+            state.append(row[0], comm)
 
     def __call__(self, m, X, y, kernel, theta, seed, comm):
+        if self.incremental:
+            return self._select_incremental(m, X, y, kernel, seed, comm)
         active = comm.sample_rows(X, 1, seed)           # 1 random start
         sigma2 = kernel.white_noise_var()
         s = math.sqrt(sigma2)

@@ -151,6 +151,17 @@ def cross_kernel(kernel: Kernel, Xtest: torch.Tensor, Xtrain: torch.Tensor):
     return kernel.cross_kernel(Xtest, Xtrain)
 
 
+def greedy_state(kernel: Kernel, X: torch.Tensor, y: torch.Tensor, m: int):
+    """State object of the incremental greedy forward selection of ``m``
+    points among the local rows (``append`` / ``scores`` / ``best``): on the
+    kernels of greedy.hip where the tree is canonical and the gate takes
+    (n, m, d), in fp64 torch otherwise (any tree, and on CPU)."""
+    hip = _backend_for("greedy_state", X)
+    if hip is not None and hip.supports_greedy(kernel, X, m):
+        return hip.GreedyState(kernel, X, y, m)
+    return torch_backend.GreedyState(kernel, X, y, m)
+
+
 def predict_stream(kernel: Kernel, X: torch.Tensor, active: torch.Tensor,
                    mv: torch.Tensor, M: torch.Tensor, with_var: bool = True,
                    chunk_rows: int = 262144, stream=True):

@@ -563,6 +563,105 @@ std::tuple<torch::Tensor, c10::optional<torch::Tensor>> ppa_predict_wide(
   return {mean, var};
 }
 
+// K15: incremental greedy forward selection (greedy.hip).  The caller owns
+// the state of a selection of m points among n rows: U fp32 and V fp64
+// [m, n_pad], row vectors of n_pad = greedy_npad(n) elements (y zero past
+// n; p, q, mu zero before the first round), partials
+// [greedy_blocks(n), m + 2].  A round with mc points already in runs pass 1,
+// then (after the host's step on sums) pass 2; both write the state in place.
+bool greedy_supported(int64_t n, int64_t m, int64_t d) {
+  return greedy_supported_nmd((long)n, (long)m, (long)d);
+}
+
+static void check_greedy_state(const torch::Tensor& S, const char* name,
+                               torch::ScalarType dtype, int64_t n,
+                               int64_t mc) {
+  check_arg(S, name, dtype, {ANY, (int64_t)gr_npad((long)n)}, true);
+  TORCH_CHECK(mc >= 0 && mc < S.size(0), "mc must be in [0, ", S.size(0),
+              ") for ", name, " of ", S.size(0), " columns, got ", mc);
+}
+
+// sums[:mc] = V[:mc] c, sums[mc] = c.c, sums[mc + 1] = c.y for the fp32
+// column c = amp Kb(q(X, xstar)), which is stored; U[mc] and p are updated.
+void greedy_pass1(torch::Tensor X, torch::Tensor xstar, torch::Tensor s2,
+                  double amp, torch::Tensor y, torch::Tensor a, double a_nn,
+                  int64_t mc, torch::Tensor U, torch::Tensor V,
+                  torch::Tensor c, torch::Tensor p, torch::Tensor partials,
+                  torch::Tensor sums, int64_t family) {
+  check_family(family);
+  check_arg(X, "X", F32, {ANY, ANY});
+  const int64_t n = X.size(0), d = X.size(1);
+  check_vec(xstar, "xstar", F32, d);
+  check_vec(s2, "s2", F32, d);
+  TORCH_CHECK(U.dim() == 2 && greedy_supported(n, U.size(0), d),
+              "unsupported (n, m, d) = (", n, ", ", U.dim() == 2 ? U.size(0)
+              : -1, ", ", d, ") for greedy_pass1; query greedy_supported");
+  const int64_t m = U.size(0), np = gr_npad((long)n);
+  check_greedy_state(U, "U", F32, n, mc);
+  check_greedy_state(V, "V", F64, n, mc);
+  TORCH_CHECK(V.size(0) == m, "V must have U's ", m, " columns, got ",
+              V.size(0));
+  check_arg(y, "y", F64, {np});
+  check_arg(a, "a", F64, {mc});
+  check_arg(c, "c", F32, {np}, true);
+  check_arg(p, "p", F64, {np}, true);
+  check_arg(partials, "partials", F64,
+            {(int64_t)gr_blocks((long)n), (int64_t)gr_pstride((long)m)}, true);
+  check_arg(sums, "sums", F64, {mc + 2}, true);
+  check_same_gpu({{&X, "X"}, {&xstar, "xstar"}, {&s2, "s2"}, {&y, "y"},
+                  {&a, "a"}, {&U, "U"}, {&V, "V"}, {&c, "c"}, {&p, "p"},
+                  {&partials, "partials"}, {&sums, "sums"}});
+  make_contiguous({&X, &xstar, &s2, &y, &a});
+  check_hip(launch_greedy_pass1(
+                X.data_ptr<float>(), xstar.data_ptr<float>(),
+                s2.data_ptr<float>(), (float)amp, y.data_ptr<double>(),
+                (const double*)a.data_ptr(), a_nn, (long)n, (int)d, (int)mc,
+                (int)m, U.data_ptr<float>(), V.data_ptr<double>(),
+                c.data_ptr<float>(), p.data_ptr<double>(),
+                partials.data_ptr<double>(), sums.data_ptr<double>(),
+                (int)family, current_stream()),
+            "greedy_pass1");
+}
+
+// V[mc], q and mu are updated; delta [n_pad] gets the scores (-inf past n)
+// and best = (max score, its lowest row).
+void greedy_pass2(torch::Tensor c, torch::Tensor y, torch::Tensor l,
+                  double l_nn, double beta_new, double kxx, double sigma2,
+                  int64_t n, int64_t mc, torch::Tensor V, torch::Tensor p,
+                  torch::Tensor q, torch::Tensor mu, torch::Tensor delta,
+                  torch::Tensor bval, torch::Tensor bidx,
+                  torch::Tensor best) {
+  TORCH_CHECK(V.dim() == 2 && greedy_supported(n, V.size(0), 1),
+              "unsupported (n, m) = (", n, ", ", V.dim() == 2 ? V.size(0)
+              : -1, ") for greedy_pass2; query greedy_supported");
+  const int64_t m = V.size(0), np = gr_npad((long)n);
+  const int64_t nb = gr_blocks((long)n);
+  check_greedy_state(V, "V", F64, n, mc);
+  check_arg(c, "c", F32, {np});
+  check_arg(y, "y", F64, {np});
+  check_arg(l, "l", F64, {mc});
+  check_arg(p, "p", F64, {np});
+  check_arg(q, "q", F64, {np}, true);
+  check_arg(mu, "mu", F64, {np}, true);
+  check_arg(delta, "delta", F64, {np}, true);
+  check_arg(bval, "bval", F64, {nb}, true);
+  check_arg(bidx, "bidx", torch::kInt64, {nb}, true);
+  check_arg(best, "best", F64, {2}, true);
+  check_same_gpu({{&c, "c"}, {&y, "y"}, {&l, "l"}, {&V, "V"}, {&p, "p"},
+                  {&q, "q"}, {&mu, "mu"}, {&delta, "delta"},
+                  {&bval, "bval"}, {&bidx, "bidx"}, {&best, "best"}});
+  make_contiguous({&c, &y, &l, &p});
+  check_hip(launch_greedy_pass2(
+                c.data_ptr<float>(), y.data_ptr<double>(),
+                (const double*)l.data_ptr(), l_nn, beta_new, kxx, sigma2,
+                (long)n, (int)mc, (int)m, V.data_ptr<double>(),
+                p.data_ptr<double>(), q.data_ptr<double>(),
+                mu.data_ptr<double>(), delta.data_ptr<double>(),
+                bval.data_ptr<double>(), (long long*)bidx.data_ptr<int64_t>(),
+                best.data_ptr<double>(), current_stream()),
+            "greedy_pass2");
+}
+
 // ---------------------------------------------------------------------------
 // K13: blocked fp64 Cholesky path (big_chol.hip) — host orchestration
 // ---------------------------------------------------------------------------
@@ -767,6 +866,38 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
           pybind11::arg("family") = (int)GEOM_FAM_RBF,
           pybind11::arg("max_blocks") = 0);
   mod.def("ppa_predict_wide_supported", &ppa_predict_wide_supported);
+  mod.def("greedy_pass1", &greedy_pass1,
+          "greedy selection round, pass 1: column c, U[mc], p and the "
+          "sums (V c, c.c, c.y) (K15, CDNA4)",
+          pybind11::arg("X"), pybind11::arg("xstar"), pybind11::arg("s2"),
+          pybind11::arg("amp"), pybind11::arg("y"), pybind11::arg("a"),
+          pybind11::arg("a_nn"), pybind11::arg("mc"), pybind11::arg("U"),
+          pybind11::arg("V"), pybind11::arg("c"), pybind11::arg("p"),
+          pybind11::arg("partials"), pybind11::arg("sums"),
+          pybind11::arg("family") = (int)GEOM_FAM_RBF);
+  mod.def("greedy_pass2", &greedy_pass2,
+          "greedy selection round, pass 2: V[mc], q, mu, the scores and "
+          "their argmax (K15, CDNA4)",
+          pybind11::arg("c"), pybind11::arg("y"), pybind11::arg("l"),
+          pybind11::arg("l_nn"), pybind11::arg("beta_new"),
+          pybind11::arg("kxx"), pybind11::arg("sigma2"), pybind11::arg("n"),
+          pybind11::arg("mc"), pybind11::arg("V"), pybind11::arg("p"),
+          pybind11::arg("q"), pybind11::arg("mu"), pybind11::arg("delta"),
+          pybind11::arg("bval"), pybind11::arg("bidx"),
+          pybind11::arg("best"));
+  mod.def("greedy_supported", &greedy_supported,
+          "shapes the greedy kernels take (memory is the caller's check)",
+          pybind11::arg("n"), pybind11::arg("m"), pybind11::arg("d"));
+  mod.def("greedy_npad", [](int64_t n) { return (int64_t)gr_npad((long)n); },
+          "rows of the greedy state: n up to whole blocks");
+  mod.def("greedy_blocks",
+          [](int64_t n) { return (int64_t)gr_blocks((long)n); });
+  mod.def("greedy_state_bytes",
+          [](int64_t n, int64_t m) {
+            return (int64_t)gr_state_bytes((long)n, (long)m);
+          },
+          "device bytes of the state of a selection of m among n rows",
+          pybind11::arg("n"), pybind11::arg("m"));
   mod.def("syrk_bf16_sync_acc", &syrk_bf16_sync_acc,
           "k-synchronized persistent SYRK for large m (CDNA4)");
   mod.def("syrk_bf16_acc", &syrk_bf16_acc,

@@ -1,7 +1,7 @@
 // Kernel geometry shared by the device code and the host-side gates: the
 // LDS budgets of the fused expert kernels and the SYRK tile constants.
 // Included by expert_nll.hip, laplace.hip, cross_syrk.hip, predict.hip,
-// predict_wide.hip (hipcc) and by
+// predict_wide.hip, greedy.hip (hipcc) and by
 // bindings.cpp (host compiler), so a *_supported() answer and the launch it
 // guards are computed by the same function.
 #pragma once
@@ -240,6 +240,50 @@ static GEOM_HD inline long ppw_grid(long t, long cus, long max_blocks) {
 // grid, never by t
 static GEOM_HD inline size_t ppw_scratch_floats(long grid, int m) {
   return (size_t)grid * PPW_R * (size_t)pp_mp(m);
+}
+
+// ---- greedy forward selection (greedy.hip) --------------------------------
+// A block owns GR_ROWS candidate rows, GR_RPL consecutive ones per lane; the
+// per-candidate state is laid out [m, n_pad] (a round's column contiguous
+// over rows) with n_pad a whole number of blocks, so the streaming loops
+// carry no row bound.
+#define GR_THREADS 256   // 4 waves
+#define GR_RPL 2         // rows per lane: 8-byte U loads, 16-byte V loads
+#define GR_ROWS (GR_THREADS * GR_RPL)
+#define GR_DBLK 16       // feature dims staged per pass of the generator
+#define GR_JT 8          // V columns per cross-lane reduction
+#define GR_JCH 256       // V columns whose per-wave sums LDS holds at a time
+#define GR_M_MAX 8192
+static_assert(GR_JCH % GR_JT == 0 && GR_JCH <= GR_THREADS,
+              "a chunk is whole tiles, and one thread sums a column");
+
+static GEOM_HD inline long gr_blocks(long n) {
+  return (n + GR_ROWS - 1) / GR_ROWS;
+}
+
+static GEOM_HD inline long gr_npad(long n) {
+  return gr_blocks(n) * GR_ROWS;
+}
+
+// doubles per block of the pass-1 partials: w [m], then sum c^2 and sum c y
+static GEOM_HD inline long gr_pstride(long m) {
+  return m + 2;
+}
+
+static GEOM_HD inline bool greedy_supported_nmd(long n, long m, long d) {
+  return n >= 1 && n <= 0x7fffffffL - GR_ROWS && m >= 1 && m <= GR_M_MAX &&
+         d >= 1 && d <= 65536;
+}
+
+// device bytes of the state of a selection of m points among n rows: U fp32
+// and V fp64 [m, n_pad], the row vectors c (fp32) and y, p, q, mu, delta
+// (fp64), the pass-1 partials and the per-block argmax
+static GEOM_HD inline size_t gr_state_bytes(long n, long m) {
+  const size_t np = (size_t)gr_npad(n), nb = (size_t)gr_blocks(n);
+  return np * (size_t)m * (sizeof(float) + sizeof(double)) +
+         np * (sizeof(float) + 5 * sizeof(double)) +
+         nb * (size_t)gr_pstride(m) * sizeof(double) +
+         nb * (sizeof(double) + sizeof(long long));
 }
 
 // ---- SYRK kernels (cross_syrk.hip) ----------------------------------------

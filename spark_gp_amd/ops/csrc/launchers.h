@@ -83,6 +83,23 @@ hipError_t launch_ppa_predict_wide(
     float* scratch, int grid, double* mean, double* var, int family,
     hipStream_t stream);
 
+// ---- greedy.hip -----------------------------------------------------------
+// One round of the incremental forward selection, with mc < m points in.
+// Row vectors hold gr_npad(n) elements, U and V [m, gr_npad(n)], partials
+// gr_blocks(n) * gr_pstride(m) doubles.  sums: [mc + 2] = (w, cc, cy).
+hipError_t launch_greedy_pass1(
+    const float* X, const float* xstar, const float* s2v, float amp,
+    const double* y, const double* a, double a_nn, long n, int d, int mc,
+    int m, float* U, const double* V, float* c, double* p, double* partials,
+    double* sums, int family, hipStream_t stream);
+
+// bval, bidx: [gr_blocks(n)]; best: (max score, its lowest row as a double)
+hipError_t launch_greedy_pass2(
+    const float* c, const double* y, const double* l, double l_nn,
+    double beta_new, double kxx, double sigma2, long n, int mc, int m,
+    double* V, const double* p, double* q, double* mu, double* delta,
+    double* bval, long long* bidx, double* best, hipStream_t stream);
+
 // ---- big_chol.hip ---------------------------------------------------------
 hipError_t launch_dpotrf_diag(double* A, long m, int jb, double* Vout,
                               int* bad, hipStream_t stream);

@@ -428,3 +428,87 @@ def cross_kernel(kernel: Kernel, Xtest: torch.Tensor,
                                s2, float(C), False, False, False,
                                family=base_family(cs.base))[0]
     return Kc.to(Xtest.dtype)
+
+
+# ---------------------------------------------------------------------------
+# K15: incremental greedy forward selection (greedy.hip)
+# ---------------------------------------------------------------------------
+
+def supports_greedy(kernel: Kernel, X: torch.Tensor, m: int) -> bool:
+    """A canonical tree on [n, d] fp32 rows whose (n, m, d)
+    ``ext.greedy_supported`` takes."""
+    if not supports_ppa(kernel, X) or X.dim() != 2:
+        return False
+    return bool(ext.greedy_supported(int(X.shape[0]), int(m),
+                                     int(X.shape[1])))
+
+
+class GreedyState(torch_backend.GreedyState):
+    """The incremental selection state on the device: U fp32 and V fp64 as
+    [m, n_pad] (a round's column contiguous over rows), the two passes of
+    ``append`` on the kernels of greedy.hip.  The host step, the allreduce
+    and the error behaviour are the base class's; a state that does not fit
+    the device's free memory is refused at construction."""
+
+    def _alloc(self, y: torch.Tensor):
+        n, m, dev = self.n, self.m, self.X.device
+        need = ext.greedy_state_bytes(n, m)
+        free = (torch.cuda.mem_get_info(dev)[0]
+                + torch.cuda.memory_reserved(dev)
+                - torch.cuda.memory_allocated(dev))
+        if need > free:
+            raise RuntimeError(
+                f"greedy selection of {m} points among {n} rows needs "
+                f"{need} bytes of device memory, {free} are free")
+        cs = compile_kernel(self.kernel)
+        theta = self.kernel.get_hyperparameters()
+        d = self.X.shape[1]
+        self._s2 = _s2_vector(cs, theta, d, dev)
+        self._amp = float(cs.amp(theta))
+        self._fam = base_family(cs.base)
+        # k(x, x) of a canonical tree is the same for every row
+        self._kxx = float(self.kernel.self_kernel(
+            torch.zeros(1, d, dtype=torch.float64))[0])
+        npad, nb = ext.greedy_npad(n), ext.greedy_blocks(n)
+        f64 = dict(dtype=torch.float64, device=dev)
+        self.y = torch.zeros(npad, **f64)
+        self.y[:n] = y
+        # no kernel reads a column before the round that writes it
+        self.U = torch.empty(m, npad, dtype=torch.float32, device=dev)
+        self.V = torch.empty(m, npad, **f64)
+        self.c = torch.empty(npad, dtype=torch.float32, device=dev)
+        self.p = torch.zeros(npad, **f64)
+        self.q = torch.zeros(npad, **f64)
+        self.mu = torch.zeros(npad, **f64)
+        self.delta = torch.empty(npad, **f64)
+        self._coef = torch.empty(m, **f64)          # a, then l, of a round
+        self._partials = torch.empty(nb, m + 2, **f64)
+        self._sums = torch.empty(m + 2, **f64)
+        self._bval = torch.empty(nb, **f64)
+        self._bidx = torch.empty(nb, dtype=torch.int64, device=dev)
+        self._best = torch.empty(2, **f64)
+
+    def _pass1(self, row, a, a_nn):
+        mc = self.mc
+        coef, sums = self._coef[:mc], self._sums[:mc + 2]
+        coef.copy_(a)
+        ext.greedy_pass1(self.X, row.reshape(-1), self._s2, self._amp,
+                         self.y, coef, a_nn, mc, self.U, self.V, self.c,
+                         self.p, self._partials, sums, family=self._fam)
+        return sums.cpu().numpy()
+
+    def _pass2(self, ell, l_nn, beta_new):
+        mc = self.mc
+        coef = self._coef[:mc]
+        coef.copy_(ell)
+        ext.greedy_pass2(self.c, self.y, coef, l_nn, beta_new, self._kxx,
+                         self.sigma2, self.n, mc, self.V, self.p, self.q,
+                         self.mu, self.delta, self._bval, self._bidx,
+                         self._best)
+
+    def scores(self):
+        return self.delta[:self.n]
+
+    def best(self):
+        val, idx = self._best.tolist()
+        return int(idx), val

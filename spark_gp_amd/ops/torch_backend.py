@@ -390,3 +390,118 @@ def laplace_evidence_compiled(cs: CompiledKernel, theta: np.ndarray,
     return float(-logZ.sum()), -grad
 
 
+
+
+class GreedyState:
+    """Incremental state of the greedy forward selection (Seeger et al.
+    2003): what ``GreedilyOptimizingActiveSetProvider`` recomputes from the
+    whole [n, mc] cross kernel each round, kept up to date from one new
+    cross-kernel column per selected point.
+
+    With Kmm = Lmm Lmm^T the active set's training kernel and
+    PD = sigma2 Kmm + sum_ranks C^T C = Lpd Lpd^T, every local row i holds
+    the columns U[:, i] = Lmm^-1 c_i and V[:, i] = Lpd^-1 c_i of its cross
+    row c_i, and p_i = |U[:, i]|^2, q_i = |V[:, i]|^2, mu_i = V[:, i].beta
+    with beta = Lpd^-1 Ky: the provider's quadratic forms c^T Kmm^-1 c,
+    c^T PD^-1 c and c^T magic.  Lmm, Lpd and beta are fp64 on the host and
+    identical on every rank; ``append`` grows them by one row (a bordered
+    Cholesky step) around two passes over the local rows, which this class
+    runs in fp64 torch — the CPU path and the oracle of the HIP state."""
+
+    def __init__(self, kernel: Kernel, X: torch.Tensor, y: torch.Tensor,
+                 m: int):
+        self.kernel, self.X, self.m = kernel, X, int(m)
+        self.n = X.shape[0]
+        self.sigma2 = float(kernel.white_noise_var())
+        self.mc = 0
+        self.active = X[:0]
+        self.Lmm = torch.zeros(self.m, self.m, dtype=torch.float64)
+        self.Lpd = torch.zeros(self.m, self.m, dtype=torch.float64)
+        self.beta = torch.zeros(self.m, dtype=torch.float64)
+        self._alloc(y)
+
+    def _alloc(self, y: torch.Tensor):
+        n, m = self.n, self.m
+        opt = dict(dtype=torch.float64, device=self.X.device)
+        self.y = y.double()
+        self.diagK = self.kernel.training_kernel_diag(self.X).double()
+        self.U = torch.zeros(m, n, **opt)
+        self.V = torch.zeros(m, n, **opt)
+        self.p = torch.zeros(n, **opt)
+        self.q = torch.zeros(n, **opt)
+        self.mu = torch.zeros(n, **opt)
+        self.delta = None
+
+    def append(self, row: torch.Tensor, comm) -> None:
+        """Take ``row`` ([d], the same on every rank) as active point number
+        ``mc``: one allreduce of mc + 2 doubles; the scores of the grown set
+        are then in ``scores()``."""
+        from ..ppa import NotPositiveDefiniteError
+        mc, sigma2 = self.mc, self.sigma2
+        if mc >= self.m:
+            raise ValueError(f"state holds {self.m} points already")
+        row = row.reshape(1, -1).to(self.X.dtype)
+        rd = row.double()
+        kss = float(self.kernel.training_kernel(rd)[0, 0])   # with noise
+        ks = self.kernel.cross_kernel(self.active.double(), rd).cpu()
+        a = torch.linalg.solve_triangular(self.Lmm[:mc, :mc], ks,
+                                          upper=False)[:, 0]
+        r = kss - float(a @ a)
+        if not r > 0.0:
+            raise NotPositiveDefiniteError()
+        a_nn = math.sqrt(r)
+        g = sigma2 * torch.linalg.solve_triangular(self.Lpd[:mc, :mc], ks,
+                                                   upper=False)[:, 0]
+        sums = torch.from_numpy(comm.allreduce_np(self._pass1(row, a, a_nn)))
+        ell = g + sums[:mc]
+        r = sigma2 * kss + float(sums[mc]) - float(ell @ ell)
+        if not r > 0.0:
+            raise NotPositiveDefiniteError()
+        l_nn = math.sqrt(r)
+        beta_new = (float(sums[mc + 1]) - float(ell @ self.beta[:mc])) / l_nn
+        self.Lmm[mc, :mc], self.Lmm[mc, mc] = a, a_nn
+        self.Lpd[mc, :mc], self.Lpd[mc, mc] = ell, l_nn
+        self.beta[mc] = beta_new
+        self._pass2(ell, l_nn, beta_new)
+        self.active = torch.cat([self.active, row], dim=0)
+        self.mc = mc + 1
+
+    def _pass1(self, row: torch.Tensor, a: torch.Tensor,
+               a_nn: float) -> np.ndarray:
+        """New column c; U[mc] = (c - U^T a) / a_nn and p; returns the local
+        (V c [mc], c.c, c.y) as fp64 numpy."""
+        mc = self.mc
+        c = self.kernel.cross_kernel(self.X, row).double()[:, 0]
+        u = (c - self.U[:mc].T @ a.to(c.device)) / a_nn
+        self.U[mc] = u
+        self.p += u * u
+        self.c = c
+        return torch.cat([self.V[:mc] @ c, (c @ c).reshape(1),
+                          (c @ self.y).reshape(1)]).cpu().numpy()
+
+    def _pass2(self, ell: torch.Tensor, l_nn: float, beta_new: float):
+        """V[mc] = (c - V^T l) / l_nn, q, mu, and the provider's score."""
+        mc, sigma2 = self.mc, self.sigma2
+        s = math.sqrt(sigma2)
+        v = (self.c - self.V[:mc].T @ ell.to(self.c.device)) / l_nn
+        self.V[mc] = v
+        self.q += v * v
+        self.mu += v * beta_new
+        li = torch.sqrt(self.diagK - self.p)
+        sl2 = (s / li) ** 2
+        xi = 1.0 / (sl2 + 1.0 - self.q)
+        kappa = xi * (1.0 + 2.0 * sl2)
+        delta = (-torch.log(s / li)
+                 - (torch.log(xi)
+                    + xi * (1.0 - kappa) / sigma2 * (self.y - self.mu) ** 2
+                    - kappa + 2.0) / 2.0)
+        self.delta = torch.nan_to_num(delta, nan=-math.inf)
+
+    def scores(self) -> torch.Tensor:
+        """The selection score of every local row, [n] fp64 (NaN as -inf)."""
+        return self.delta
+
+    def best(self):
+        """(local row index, score) of the best local candidate."""
+        i = int(self.delta.argmax())
+        return i, float(self.delta[i])
