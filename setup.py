@@ -28,6 +28,7 @@ ext = CUDAExtension(
         "spark_gp_amd/ops/csrc/predict.hip",
         "spark_gp_amd/ops/csrc/predict_wide.hip",
         "spark_gp_amd/ops/csrc/greedy.hip",
+        "spark_gp_amd/ops/csrc/kmeans.hip",
         "spark_gp_amd/ops/csrc/big_chol.hip",
         "spark_gp_amd/ops/csrc/synth.hip",
     ],

@@ -36,13 +36,38 @@ class RandomActiveSetProvider(ActiveSetProvider):
 class KMeansActiveSetProvider(ActiveSetProvider):
     """Lloyd iterations over the sharded data; per-iteration allreduce of
     (centroid sums, counts) — C9 in SURVEY.md §2.5.  Centroids are synthetic
-    points, matching the reference's use of MLlib cluster centers."""
+    points, matching the reference's use of MLlib cluster centers.
 
-    def __init__(self, max_iter: int = 20, chunk_rows: int = 1 << 18):
+    ``fused=True`` runs each iteration's local work as one
+    ``ops.kmeans_step``: on GPU the kernels of kmeans.hip (no [chunk, m]
+    score matrix, no atomics, so the same centres to the bit on every run),
+    on CPU the arithmetic below.  Near-ties may fall to another centre than
+    with ``fused=False``, which is why it is not the default."""
+
+    def __init__(self, max_iter: int = 20, chunk_rows: int = 1 << 18,
+                 fused: bool = False):
         self.max_iter = max_iter
         self.chunk_rows = chunk_rows
+        self.fused = bool(fused)
+
+    def _fused(self, m, X, seed, comm):
+        from . import ops
+        centers = comm.sample_rows(X, m, seed)          # seeded init
+        work = {}                                       # the step's buffers
+        for _ in range(self.max_iter):
+            sums, counts, _ = ops.kmeans_step(X, centers, self.chunk_rows,
+                                              work)
+            comm.allreduce_(sums)
+            comm.allreduce_(counts)
+            nonempty = counts > 0
+            centers = centers.clone()
+            centers[nonempty] = (sums[nonempty]
+                                 / counts[nonempty].unsqueeze(-1)).to(X.dtype)
+        return centers
 
     def __call__(self, m, X, y, kernel, theta, seed, comm):
+        if self.fused:
+            return self._fused(m, X, seed, comm)
         centers = comm.sample_rows(X, m, seed)          # seeded init
         n, d = X.shape
         for _ in range(self.max_iter):

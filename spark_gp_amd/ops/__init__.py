@@ -162,6 +162,19 @@ def greedy_state(kernel: Kernel, X: torch.Tensor, y: torch.Tensor, m: int):
     return torch_backend.GreedyState(kernel, X, y, m)
 
 
+def kmeans_step(X: torch.Tensor, centers: torch.Tensor,
+                chunk_rows: int = 1 << 18, work=None):
+    """One Lloyd step, ``(sums, counts, assign)`` with fp64 sums [m, d] and
+    counts [m]: on the kernels of kmeans.hip where the gate takes X and the
+    centres (contiguous fp32, m up to 8192), in torch over chunks of
+    ``chunk_rows`` rows otherwise (any dtype, and on CPU).  ``work``: a dict
+    the caller keeps across the steps of a loop, for the HIP buffers."""
+    hip = _backend_for("kmeans_step", X)
+    if hip is not None and hip.supports_kmeans(X, centers):
+        return hip.kmeans_step(X, centers, work)
+    return torch_backend.kmeans_step(X, centers, chunk_rows, work)
+
+
 def predict_stream(kernel: Kernel, X: torch.Tensor, active: torch.Tensor,
                    mv: torch.Tensor, M: torch.Tensor, with_var: bool = True,
                    chunk_rows: int = 262144, stream=True):

@@ -662,6 +662,68 @@ void greedy_pass2(torch::Tensor c, torch::Tensor y, torch::Tensor l,
             "greedy_pass2");
 }
 
+// K16: one k-means Lloyd step (kmeans.hip).  The caller owns the work
+// buffers, so a loop of steps allocates them once: assign [kmeans_npad(n)]
+// int32, c2 [kmeans_mpad(m)] fp32 and partials [kmeans_partial_doubles(n, m,
+// d)] fp64 are scratch, sums [m, d] and counts [m] fp64 the result.
+bool kmeans_supported(int64_t n, int64_t m, int64_t d) {
+  return kmeans_supported_nmd((long)n, (long)m, (long)d);
+}
+
+// X's shape, checked against the gate; the rows are read in place
+static void check_kmeans_rows(const torch::Tensor& X, int64_t m,
+                              const char* what) {
+  check_arg(X, "X", F32, {ANY, ANY}, true);
+  TORCH_CHECK(kmeans_supported(X.size(0), m, X.size(1)),
+              "unsupported (n, m, d) = (", X.size(0), ", ", m, ", ",
+              X.size(1), ") for ", what, "; query kmeans_supported");
+}
+
+// assign[i] = argmin_j ||c_j||^2 - 2 x_i.c_j, the lowest j among equal
+// scores; -1 past n
+void kmeans_assign(torch::Tensor X, torch::Tensor centers, torch::Tensor c2,
+                   torch::Tensor assign) {
+  TORCH_CHECK(centers.dim() == 2, "centers must be [m, d], got ",
+              centers.sizes());
+  const int64_t m = centers.size(0);
+  check_kmeans_rows(X, m, "kmeans_assign");
+  const int64_t n = X.size(0), d = X.size(1);
+  check_arg(centers, "centers", F32, {m, d});
+  check_arg(c2, "c2", F32, {(int64_t)km_mpad((int)m)}, true);
+  check_arg(assign, "assign", I32, {(int64_t)km_npad((long)n)}, true);
+  check_same_gpu({{&X, "X"}, {&centers, "centers"}, {&c2, "c2"},
+                  {&assign, "assign"}});
+  make_contiguous({&centers});
+  check_hip(launch_kmeans_assign(X.data_ptr<float>(),
+                                 centers.data_ptr<float>(), (long)n, (int)m,
+                                 (int)d, c2.data_ptr<float>(),
+                                 assign.data_ptr<int>(), current_stream()),
+            "kmeans_assign");
+}
+
+// sums[j] = sum of the rows with assign == j, counts[j] their number; a row
+// whose assign is outside [0, m) counts nowhere
+void kmeans_accumulate(torch::Tensor X, torch::Tensor assign,
+                       torch::Tensor partials, torch::Tensor sums,
+                       torch::Tensor counts) {
+  TORCH_CHECK(sums.dim() == 2, "sums must be [m, d], got ", sums.sizes());
+  const int64_t m = sums.size(0);
+  check_kmeans_rows(X, m, "kmeans_accumulate");
+  const int64_t n = X.size(0), d = X.size(1);
+  check_arg(assign, "assign", I32, {(int64_t)km_npad((long)n)}, true);
+  check_arg(partials, "partials", F64,
+            {(int64_t)km_partial_doubles((long)n, (long)m, (long)d)}, true);
+  check_arg(sums, "sums", F64, {m, d}, true);
+  check_arg(counts, "counts", F64, {m}, true);
+  check_same_gpu({{&X, "X"}, {&assign, "assign"}, {&partials, "partials"},
+                  {&sums, "sums"}, {&counts, "counts"}});
+  check_hip(launch_kmeans_accumulate(
+                X.data_ptr<float>(), assign.data_ptr<int>(), (long)n, (int)m,
+                (int)d, partials.data_ptr<double>(), sums.data_ptr<double>(),
+                counts.data_ptr<double>(), current_stream()),
+            "kmeans_accumulate");
+}
+
 // ---------------------------------------------------------------------------
 // K13: blocked fp64 Cholesky path (big_chol.hip) — host orchestration
 // ---------------------------------------------------------------------------
@@ -898,6 +960,32 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
           },
           "device bytes of the state of a selection of m among n rows",
           pybind11::arg("n"), pybind11::arg("m"));
+  mod.def("kmeans_assign", &kmeans_assign,
+          "Lloyd step, part 1: every row's nearest centroid, no [n, m] "
+          "array (K16, CDNA4)",
+          pybind11::arg("X"), pybind11::arg("centers"), pybind11::arg("c2"),
+          pybind11::arg("assign"));
+  mod.def("kmeans_accumulate", &kmeans_accumulate,
+          "Lloyd step, part 2: fp64 sums and counts per centroid in a fixed "
+          "order, no atomics (K16, CDNA4)",
+          pybind11::arg("X"), pybind11::arg("assign"),
+          pybind11::arg("partials"), pybind11::arg("sums"),
+          pybind11::arg("counts"));
+  mod.def("kmeans_supported", &kmeans_supported,
+          "shapes the k-means kernels take (memory is the caller's check)",
+          pybind11::arg("n"), pybind11::arg("m"), pybind11::arg("d"));
+  mod.def("kmeans_slice_rows", []() { return (int64_t)KM_SLICE; },
+          "rows of one fp32 accumulation of kmeans_accumulate");
+  mod.def("kmeans_npad", [](int64_t n) { return (int64_t)km_npad((long)n); },
+          "elements of assign: n up to whole row tiles");
+  mod.def("kmeans_mpad", [](int64_t m) { return (int64_t)km_mpad((int)m); },
+          "elements of c2: m up to whole centroid panels");
+  mod.def("kmeans_partial_doubles",
+          [](int64_t n, int64_t m, int64_t d) {
+            return (int64_t)km_partial_doubles((long)n, (long)m, (long)d);
+          },
+          "elements of the partials of kmeans_accumulate",
+          pybind11::arg("n"), pybind11::arg("m"), pybind11::arg("d"));
   mod.def("syrk_bf16_sync_acc", &syrk_bf16_sync_acc,
           "k-synchronized persistent SYRK for large m (CDNA4)");
   mod.def("syrk_bf16_acc", &syrk_bf16_acc,

@@ -1,7 +1,7 @@
 // Kernel geometry shared by the device code and the host-side gates: the
 // LDS budgets of the fused expert kernels and the SYRK tile constants.
 // Included by expert_nll.hip, laplace.hip, cross_syrk.hip, predict.hip,
-// predict_wide.hip, greedy.hip (hipcc) and by
+// predict_wide.hip, greedy.hip, kmeans.hip (hipcc) and by
 // bindings.cpp (host compiler), so a *_supported() answer and the launch it
 // guards are computed by the same function.
 #pragma once
@@ -284,6 +284,105 @@ static GEOM_HD inline size_t gr_state_bytes(long n, long m) {
          np * (sizeof(float) + 5 * sizeof(double)) +
          nb * (size_t)gr_pstride(m) * sizeof(double) +
          nb * (sizeof(double) + sizeof(long long));
+}
+
+// ---- k-means Lloyd step (kmeans.hip) --------------------------------------
+// Assign: a block owns KM_ROWS rows (a 64-row group of four 16-row MFMA
+// tiles per wave) and walks the centroids in panels of KM_PANEL, KM_DBLK
+// dims at a time.  Accumulate: a block owns KM_SLAB centroids (32 per wave),
+// a panel of up to KM_DPANEL of the d + 1 columns (the dims, then the ones
+// column that counts) and one slice of KM_SLICE rows, staged KM_RCH rows at
+// a time.  Every grid depends on (n, m, d) and these constants only.
+#define KM_THREADS 256   // 4 waves
+#define KM_ROWS 256
+#define KM_PANEL 64
+#define KM_DBLK PP_DBLK
+// The assign kernel keeps its X tile in LDS across panels up to this many
+// (KM_DBLK-padded) dims: 256 x 66 x 4 B + the panel = 76 KiB, two blocks per
+// CU.  Above it the tile is staged again for every panel.
+#define KM_XRES_DMAX 64
+// LDS row stride of the assign kernel's X tile (dp dims wide) and centroid
+// panel.  = 2 (mod 4): a fragment read t[i][k0 + (l>>4)], i = l&15, touches
+// bank 2 i u + (l>>4) (mod 32) with u odd, 32 distinct banks in each 32-lane
+// group (pp_cstr's argument).
+#define KM_STR(dp) ((dp) + 2)
+#define KM_SLAB 128
+#define KM_DPANEL 128
+#define KM_RCH 128
+#define KM_SLICE 2048    // rows of one fp32 accumulation: exact counts < 2^24
+#define KM_M_MAX 8192
+static_assert(KM_ROWS == 64 * (KM_THREADS / 64), "a 64-row group per wave");
+static_assert(KM_SLAB == 32 * (KM_THREADS / 64), "32 centroids per wave");
+static_assert(KM_SLICE % KM_RCH == 0 && KM_RCH % 4 == 0, "whole k steps");
+
+static GEOM_HD inline long km_blocks(long n) {
+  return (n + KM_ROWS - 1) / KM_ROWS;
+}
+
+// elements of assign: n up to whole row tiles, -1 past n
+static GEOM_HD inline long km_npad(long n) {
+  return km_blocks(n) * KM_ROWS;
+}
+
+// elements of the centroid norms: m up to whole panels, +inf past m
+static GEOM_HD inline int km_mpad(int m) {
+  return (m + KM_PANEL - 1) / KM_PANEL * KM_PANEL;
+}
+
+// dims of the assign kernel's LDS X tile: all of d (padded) while resident
+static GEOM_HD inline int km_xdims(int d) {
+  const int dp = (d + KM_DBLK - 1) / KM_DBLK * KM_DBLK;
+  return dp <= KM_XRES_DMAX ? dp : KM_DBLK;
+}
+
+// 16-row tiles per wave of the assign kernel: below KM_SMALL_N rows 256-row
+// tiles make fewer than 256 blocks, so a block takes 64 rows.  A function of
+// n alone, and a row's scores do not depend on the tiling.
+#define KM_SMALL_N 65536
+static GEOM_HD inline int km_row_tiles(long n) {
+  return n <= KM_SMALL_N ? 1 : 4;
+}
+
+// LDS bytes of kmeans_assign_kernel on `rows` rows; region order is its carve
+static GEOM_HD inline size_t km_assign_lds_bytes(int rows, int d) {
+  return a16(sizeof(float) * rows * KM_STR(km_xdims(d))) +
+         a16(sizeof(float) * KM_PANEL * KM_STR(KM_DBLK));
+}
+
+static GEOM_HD inline long km_slices(long n) {
+  return (n + KM_SLICE - 1) / KM_SLICE;
+}
+
+// the d + 1 columns of the accumulate kernel in 16-column MFMA tiles, split
+// evenly over the fewest panels of at most KM_DPANEL columns
+static GEOM_HD inline int km_panels(int d) {
+  return (d + 1 + KM_DPANEL - 1) / KM_DPANEL;
+}
+
+static GEOM_HD inline int km_panel_tiles(int d) {
+  const int tiles = (d + 1 + 15) / 16, panels = km_panels(d);
+  return (tiles + panels - 1) / panels;
+}
+
+// LDS row stride of the accumulate kernel's X chunk of ndt column tiles.
+// = 16 (mod 32): the B-fragment read xs[k0 + (l>>4)][j0 + (l&15)] of a
+// 32-lane group is two rows of 16 contiguous floats that start 16 banks
+// apart, 32 distinct banks.
+static GEOM_HD inline int km_acc_str(int ndt) {
+  return ((16 * ndt + 31) & ~31) + 16;
+}
+
+// doubles of the accumulate kernel's partials: [slices, m, d + 1]
+static GEOM_HD inline size_t km_partial_doubles(long n, long m, long d) {
+  return (size_t)km_slices(n) * (size_t)m * (size_t)(d + 1);
+}
+
+// d: no register or LDS plan depends on it (the assign kernel walks it in
+// chunks, the accumulate kernel in panels over the grid's z), so the bound
+// is the 65535 panels of a grid, cut to the 65536 of the other gates
+static GEOM_HD inline bool kmeans_supported_nmd(long n, long m, long d) {
+  return n >= 1 && n <= 0x7fffffffL - KM_ROWS && m >= 1 && m <= KM_M_MAX &&
+         d >= 1 && d <= 65536;
 }
 
 // ---- SYRK kernels (cross_syrk.hip) ----------------------------------------

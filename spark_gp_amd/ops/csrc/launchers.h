@@ -100,6 +100,21 @@ hipError_t launch_greedy_pass2(
     double* V, const double* p, double* q, double* mu, double* delta,
     double* bval, long long* bidx, double* best, hipStream_t stream);
 
+// ---- kmeans.hip -----------------------------------------------------------
+// One Lloyd step in two launches joined by assign [km_npad(n)]: the nearest
+// centroid of every row (-1 past n; lowest index among equal scores), then
+// fp64 sums [m, d] and counts [m] of the rows of each centroid.
+// c2: km_mpad(m) floats of scratch (the centroid norms)
+hipError_t launch_kmeans_assign(const float* X, const float* C, long n, int m,
+                                int d, float* c2, int* assign,
+                                hipStream_t stream);
+
+// partials: km_partial_doubles(n, m, d) doubles of scratch
+hipError_t launch_kmeans_accumulate(const float* X, const int* assign, long n,
+                                    int m, int d, double* partials,
+                                    double* sums, double* counts,
+                                    hipStream_t stream);
+
 // ---- big_chol.hip ---------------------------------------------------------
 hipError_t launch_dpotrf_diag(double* A, long m, int jb, double* Vout,
                               int* bad, hipStream_t stream);

@@ -512,3 +512,43 @@ class GreedyState(torch_backend.GreedyState):
     def best(self):
         val, idx = self._best.tolist()
         return int(idx), val
+
+
+# ---------------------------------------------------------------------------
+# K16: k-means Lloyd step (kmeans.hip)
+# ---------------------------------------------------------------------------
+
+def supports_kmeans(X: torch.Tensor, centers: torch.Tensor) -> bool:
+    """Contiguous fp32 rows [n, d] and fp32 centres [m, d] whose (n, m, d)
+    ``ext.kmeans_supported`` takes."""
+    if X.dim() != 2 or centers.dim() != 2 or X.shape[1] != centers.shape[1]:
+        return False
+    if X.dtype != torch.float32 or centers.dtype != torch.float32:
+        return False
+    return X.is_contiguous() and bool(ext.kmeans_supported(
+        int(X.shape[0]), int(centers.shape[0]), int(X.shape[1])))
+
+
+def kmeans_step(X: torch.Tensor, centers: torch.Tensor, work=None):
+    """``torch_backend.kmeans_step`` on the kernels of kmeans.hip: no [n, m]
+    array, no atomics, the same bits on every run.  ``assign`` is int32 and
+    takes the lowest index among equal scores.  ``work``: a dict that keeps
+    the buffers (assign, norms, partials) between the steps of one loop."""
+    n, d = X.shape
+    m = centers.shape[0]
+    work = {} if work is None else work
+    if work.get("key") != (n, m, d, X.device):
+        dev = X.device
+        work.clear()
+        work["key"] = (n, m, d, dev)
+        work["assign"] = torch.empty(ext.kmeans_npad(n), dtype=torch.int32,
+                                     device=dev)
+        work["c2"] = torch.empty(ext.kmeans_mpad(m), dtype=torch.float32,
+                                 device=dev)
+        work["partials"] = torch.empty(ext.kmeans_partial_doubles(n, m, d),
+                                       dtype=torch.float64, device=dev)
+    sums = torch.empty(m, d, dtype=torch.float64, device=X.device)
+    counts = torch.empty(m, dtype=torch.float64, device=X.device)
+    ext.kmeans_assign(X, centers, work["c2"], work["assign"])
+    ext.kmeans_accumulate(X, work["assign"], work["partials"], sums, counts)
+    return sums, counts, work["assign"][:n]

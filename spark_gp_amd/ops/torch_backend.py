@@ -390,6 +390,30 @@ def laplace_evidence_compiled(cs: CompiledKernel, theta: np.ndarray,
     return float(-logZ.sum()), -grad
 
 
+def kmeans_step(X: torch.Tensor, centers: torch.Tensor,
+                chunk_rows: int = 1 << 18, work=None):
+    """One Lloyd step over the rows of X: fp64 ``sums`` [m, d] and ``counts``
+    [m] of the rows nearest to each centre, and ``assign`` [n].  The
+    arithmetic of ``KMeansActiveSetProvider``'s loop body, term for term and
+    chunk for chunk; the CPU path and the oracle of the HIP step (``work``
+    is that backend's buffer cache, unused here)."""
+    n, d = X.shape
+    m = centers.shape[0]
+    sums = torch.zeros(m, d, dtype=torch.float64, device=X.device)
+    counts = torch.zeros(m, dtype=torch.float64, device=X.device)
+    assign = torch.empty(n, dtype=torch.int64, device=X.device)
+    c2 = (centers * centers).sum(-1)
+    for s in range(0, n, chunk_rows):
+        xb = X[s:min(n, s + chunk_rows)]
+        # argmin_j ||x - c_j||^2 = argmin_j (||c_j||^2 - 2 x.c_j)
+        a = (c2 - 2.0 * (xb @ centers.T)).argmin(-1)
+        sums.index_add_(0, a, xb.double())
+        counts.index_add_(0, a,
+                          torch.ones(len(xb), dtype=torch.float64,
+                                     device=X.device))
+        assign[s:s + len(xb)] = a
+    return sums, counts, assign
+
 
 
 class GreedyState:
