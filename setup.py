@@ -25,6 +25,8 @@ ext = CUDAExtension(
         "spark_gp_amd/ops/csrc/expert_nll_m52.hip",
         "spark_gp_amd/ops/csrc/cross_syrk.hip",
         "spark_gp_amd/ops/csrc/laplace.hip",
+        "spark_gp_amd/ops/csrc/laplace_m32.hip",
+        "spark_gp_amd/ops/csrc/laplace_m52.hip",
         "spark_gp_amd/ops/csrc/predict.hip",
         "spark_gp_amd/ops/csrc/predict_wide.hip",
         "spark_gp_amd/ops/csrc/greedy.hip",

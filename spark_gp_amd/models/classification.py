@@ -25,11 +25,13 @@ from .predictor import GaussianProjectedProcessRawPredictor
 class GaussianProcessClassifier(GaussianProcessCommons):
     _PARAMS = dict(GaussianProcessCommons._PARAMS,
                    max_newton_iter="_max_newton_iter",
-                   link="_link")
+                   link="_link",
+                   fused_matern="_fused_matern")
 
     def __init__(self, **params):
         self._max_newton_iter = 200
         self._link = "logistic"
+        self._fused_matern = False
         super().__init__(**params)
 
     def setMaxNewtonIter(self, v: int):
@@ -44,6 +46,14 @@ class GaussianProcessClassifier(GaussianProcessCommons):
         if link not in ("logistic", "probit"):
             raise ValueError("link must be 'logistic' or 'probit'")
         self._link = link
+        return self
+
+    def setFusedMatern(self, v: bool):
+        """Opt in to the fused HIP Laplace kernels for the Matern 3/2 and 5/2
+        bases ('m32', 'ard_m32', 'm52', 'ard_m52') under the logistic link.
+        Default False: those bases take the batched torch Newton loop, as
+        before; RBF bases take the fused kernels either way."""
+        self._fused_matern = bool(v)
         return self
 
     def _resolve_likelihood(self):
@@ -75,7 +85,8 @@ class GaussianProcessClassifier(GaussianProcessCommons):
             for (idx, Xg, yg), fg in zip(groups, fs):
                 nll, grad = ops.laplace_nll_grad(
                     kernel, theta, Xg, yg, fg, self._tol,
-                    self._max_newton_iter, likelihood=lik)
+                    self._max_newton_iter, likelihood=lik,
+                    fused_matern=self._fused_matern)
                 nll_total += nll
                 grad_total += grad
             return nll_total, grad_total

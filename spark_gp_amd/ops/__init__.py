@@ -82,7 +82,10 @@ def nll_grad_generic(kernel: Kernel, theta: np.ndarray,
 
 def laplace_nll_grad(kernel: Kernel, theta: np.ndarray, X: torch.Tensor,
                      y: torch.Tensor, f: torch.Tensor, tol: float,
-                     max_newton_iter: int = 200, likelihood=None):
+                     max_newton_iter: int = 200, likelihood=None,
+                     fused_matern: bool = False):
+    """``fused_matern``: let the Matern 3/2 and 5/2 bases take the fused HIP
+    Laplace kernels as well (opt-in; the RBF bases always do)."""
     from ..kernels.compiled import compile_kernel
     from ..likelihoods import LogisticLikelihood
     logistic = likelihood is None or isinstance(likelihood,
@@ -93,7 +96,7 @@ def laplace_nll_grad(kernel: Kernel, theta: np.ndarray, X: torch.Tensor,
     hip = _backend_for("laplace_nll_grad", X) if cs is not None else None
     if hip is not None:
         if tol >= hip.LAPLACE_MIN_TOL and \
-                hip.supports_laplace_evidence(cs, X):
+                hip.supports_laplace_evidence(cs, X, fused_matern):
             # fully fused K10+K11: Newton AND the Algorithm 5.1 evidence
             # in one launch; None -> fp32 breakdown, warm torch fallback
             res = hip.laplace_evidence(cs, theta, X, y, f, tol,
@@ -102,7 +105,7 @@ def laplace_nll_grad(kernel: Kernel, theta: np.ndarray, X: torch.Tensor,
                 return res
             return torch_backend.laplace_nll_grad(
                 kernel, theta, X, y, f, tol, max_newton_iter)
-        if hip.supports_laplace(cs, X):
+        if hip.supports_laplace(cs, X, fused_matern):
             # fused Newton loop runs each expert to convergence on the GPU
             # (updates f in place); the torch pass below then converges in
             # 2-3 cheap iterations and computes the Algorithm 5.1 evidence

@@ -417,12 +417,14 @@ void colsum_gemv_acc(torch::Tensor Kc, torch::Tensor y, torch::Tensor Ky) {
 // iters = 0, and with EV = true the tail evaluates Algorithm 5.1 (logz and
 // grad) at the given latent, converged or not — the exit state is recomputed
 // at f, nothing is carried over from an iteration.
+// family: the covariance family of the base kernel (default RBF).
 template <bool EV>
 std::vector<torch::Tensor> fused_laplace(torch::Tensor X, torch::Tensor y,
                                          torch::Tensor f, torch::Tensor scale,
                                          double amp, double noise, double tol,
-                                         int64_t max_newton) {
+                                         int64_t max_newton, int64_t family) {
   const char* what = EV ? "fused_laplace_evidence" : "fused_laplace_newton";
+  check_family(family);
   check_arg(X, "X", F32, {ANY, ANY, ANY});
   const int E = X.size(0), k = X.size(1), d = X.size(2);
   check_arg(y, "y", F32, {E, k});
@@ -440,7 +442,7 @@ std::vector<torch::Tensor> fused_laplace(torch::Tensor X, torch::Tensor y,
                   f.data_ptr<float>(), scale.data_ptr<float>(), (float)amp,
                   (float)noise, E, k, d, tol, (int)max_newton,
                   psi.data_ptr<double>(), sll.data_ptr<double>(),
-                  iters.data_ptr<int>(), bad.data_ptr<int>(),
+                  iters.data_ptr<int>(), bad.data_ptr<int>(), (int)family,
                   current_stream()),
               what);
     return {psi, sll, iters, bad};
@@ -454,7 +456,7 @@ std::vector<torch::Tensor> fused_laplace(torch::Tensor X, torch::Tensor y,
                 psi.data_ptr<double>(), sll.data_ptr<double>(),
                 iters.data_ptr<int>(), bad.data_ptr<int>(),
                 logz.data_ptr<double>(), grad.data_ptr<double>(),
-                current_stream()),
+                (int)family, current_stream()),
             what);
   return {logz, grad, iters, bad};
 }
@@ -863,10 +865,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
           pybind11::arg("rhs_identity") = false);
   mod.def("dgemm64", &dgemm64, "fp64 MFMA GEMM (test/utility)");
   mod.def("fused_laplace_newton", &fused_laplace<false>,
-          "per-expert Laplace Newton loop to convergence (CDNA4)");
+          "per-expert Laplace Newton loop to convergence (CDNA4)",
+          pybind11::arg("X"), pybind11::arg("y"), pybind11::arg("f"), pybind11::arg("scale"), pybind11::arg("amp"),
+          pybind11::arg("noise"), pybind11::arg("tol"), pybind11::arg("max_newton"),
+          pybind11::arg("family") = (int)GEOM_FAM_RBF);
   mod.def("fused_laplace_newton_supported", &fused_laplace_newton_supported);
   mod.def("fused_laplace_evidence", &fused_laplace<true>,
-          "fused Newton + Algorithm 5.1 evidence/gradient (K11, CDNA4)");
+          "fused Newton + Algorithm 5.1 evidence/gradient (K11, CDNA4)",
+          pybind11::arg("X"), pybind11::arg("y"), pybind11::arg("f"), pybind11::arg("scale"), pybind11::arg("amp"),
+          pybind11::arg("noise"), pybind11::arg("tol"), pybind11::arg("max_newton"),
+          pybind11::arg("family") = (int)GEOM_FAM_RBF);
   mod.def("fused_laplace_evidence_supported",
           &fused_laplace_evidence_supported);
   mod.def("fused_expert_nll", &fused_expert_nll,

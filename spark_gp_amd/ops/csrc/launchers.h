@@ -24,17 +24,19 @@ hipError_t launch_fused_expert_nll(
 hipError_t fused_expert_nll_resident_wgs(int k, int d, int family, int* out);
 
 // ---- laplace.hip ----------------------------------------------------------
+// (these two answer an unknown family, like an unsupported (k, d), with
+// hipErrorInvalidConfiguration)
 hipError_t launch_fused_laplace_newton(
     const float* X, const float* y, float* f, const float* scale, float amp,
     float noise, int E, int k, int d, double tol, int max_newton,
     double* out_psi, double* out_sumlogl, int* out_iters, int* out_bad,
-    hipStream_t stream);
+    int family, hipStream_t stream);
 
 hipError_t launch_fused_laplace_evidence(
     const float* X, const float* y, float* f, const float* scale, float amp,
     float noise, int E, int k, int d, double tol, int max_newton,
     double* out_psi, double* out_sumlogl, int* out_iters, int* out_bad,
-    double* out_logz, double* out_grad, hipStream_t stream);
+    double* out_logz, double* out_grad, int family, hipStream_t stream);
 
 // ---- cross_syrk.hip -------------------------------------------------------
 hipError_t launch_cross_kernel_tile(

@@ -17,7 +17,7 @@ import numpy as np
 import torch
 
 from ..kernels.base import Kernel
-from ..kernels.compiled import (BASES, RBF_BASES, CompiledKernel,
+from ..kernels.compiled import (BASES, FAM_RBF, RBF_BASES, CompiledKernel,
                                 base_family, base_scale, compile_kernel)
 from .. import _hip_ext as ext
 from . import torch_backend
@@ -105,10 +105,11 @@ LAPLACE_MIN_TOL = float(os.environ.get("SPARK_GP_AMD_LAPLACE_MIN_TOL",
                                        "1e-6"))
 
 
-def supports_laplace(cs: CompiledKernel, X: torch.Tensor) -> bool:
-    # laplace.hip is exp(-q) only
+def supports_laplace(cs: CompiledKernel, X: torch.Tensor,
+                     matern: bool = False) -> bool:
+    # laplace.hip has every family; the Matern ones are opt-in
     return _supports_expert(cs, X, ext.fused_laplace_newton_supported,
-                            RBF_BASES)
+                            BASES if matern else RBF_BASES)
 
 
 def _fused_laplace(entry, cs: CompiledKernel, theta: np.ndarray,
@@ -122,9 +123,13 @@ def _fused_laplace(entry, cs: CompiledKernel, theta: np.ndarray,
     if not f.is_contiguous():
         raise ValueError("latent f must be contiguous")
     scale = _scale_vector(cs, theta, X.shape[-1], X.device)
+    fam = base_family(cs.base)
+    # an RBF call is the call it always was; only the Matern families name
+    # theirs
+    kw = {"family": fam} if fam != FAM_RBF else {}
     return entry(X, y.to(torch.float32), f, scale, float(cs.amp(theta)),
                  float(cs.noise(theta)), max(float(tol), LAPLACE_MIN_TOL),
-                 min(int(max_newton), 40))
+                 min(int(max_newton), 40), **kw)
 
 
 def laplace_newton(cs: CompiledKernel, theta: np.ndarray, X: torch.Tensor,
@@ -139,9 +144,10 @@ def laplace_newton(cs: CompiledKernel, theta: np.ndarray, X: torch.Tensor,
     return int((bad != 0).sum())
 
 
-def supports_laplace_evidence(cs: CompiledKernel, X: torch.Tensor) -> bool:
+def supports_laplace_evidence(cs: CompiledKernel, X: torch.Tensor,
+                              matern: bool = False) -> bool:
     return _supports_expert(cs, X, ext.fused_laplace_evidence_supported,
-                            RBF_BASES)
+                            BASES if matern else RBF_BASES)
 
 
 def laplace_evidence(cs: CompiledKernel, theta: np.ndarray, X: torch.Tensor,
