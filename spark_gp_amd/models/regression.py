@@ -28,6 +28,22 @@ from .predictor import GaussianProjectedProcessRawPredictor
 
 
 class GaussianProcessRegression(GaussianProcessCommons):
+    _PARAMS = dict(GaussianProcessCommons._PARAMS,
+                   fused_large_experts="_fused_large_experts")
+
+    def __init__(self, **params):
+        self._fused_large_experts = False
+        super().__init__(**params)
+
+    def setFusedLargeExperts(self, v: bool):
+        """Opt in to the fused HIP panel kernel for experts of more than 128
+        rows (``setDatasetSizeForExpert`` up to 1024, d <= 128, fp32 on the
+        GPU).  Default False: such experts take the batched torch objective,
+        as before; experts of up to 128 rows take the resident fused kernel
+        either way."""
+        self._fused_large_experts = bool(v)
+        return self
+
     def fit(self, X, y) -> "GaussianProcessRegressionModel":
         instr = Instrumentation("GaussianProcessRegression")
         comm = get_comm()
@@ -42,7 +58,8 @@ class GaussianProcessRegression(GaussianProcessCommons):
             grad_total = np.zeros_like(theta)
             for _, Xg, yg in groups:
                 if cs is not None:
-                    nll, grad = ops.nll_grad_compiled(cs, theta, Xg, yg)
+                    nll, grad = ops.nll_grad_compiled(
+                        cs, theta, Xg, yg, panel=self._fused_large_experts)
                 else:
                     nll, grad = ops.nll_grad_generic(kernel, theta, Xg, yg)
                 nll_total += nll

@@ -66,12 +66,18 @@ def _backend_for(what: str, t: torch.Tensor, required: bool = True):
 
 
 def nll_grad_compiled(cs: CompiledKernel, theta: np.ndarray,
-                      X: torch.Tensor, y: torch.Tensor
+                      X: torch.Tensor, y: torch.Tensor, panel: bool = False
                       ) -> Tuple[float, np.ndarray]:
+    """``panel``: let experts of 128 < k <= 1024 rows (d <= 128, fp32, on
+    the GPU) take the fused HIP panel kernel.  Default False: those shapes
+    take the batched torch path, as before; every other input takes the
+    path it always took, whatever ``panel`` says."""
     hip = (_backend_for("nll_grad_compiled", X)
            if cs.base in BASES else None)
     if hip is not None and hip.supports_nll(cs, X):
         return hip.nll_grad_compiled(cs, theta, X, y)
+    if panel and hip is not None and hip.supports_nll_panel(cs, X):
+        return hip.nll_grad_compiled(cs, theta, X, y, panel=True)
     return torch_backend.nll_grad_compiled(cs, theta, X, y)
 
 

@@ -159,6 +159,82 @@ int64_t fused_expert_nll_occupancy(int64_t k, int64_t d, int64_t family) {
   return wgs;
 }
 
+// The same five outputs for experts of 128 < k <= 1024 rows
+// (expert_nll_panel.hip).  Persistent workgroups keep the matrix of the
+// expert they are on in a scratch of grid x kp x kp floats, allocated here:
+// grid = min(E, resident workgroups, what NLP_SCRATCH_MAX_BYTES holds,
+// max_blocks if > 0), so it never grows with E.  The kernel reads X in
+// place: a non-contiguous X is refused, not copied.  sb: the super-block, 64
+// or 128 (0: nlp_sb_default(k)); an expert's outputs depend on sb, never on
+// the grid.
+bool fused_expert_nll_panel_supported(int64_t k, int64_t d) {
+  return nlp_supported_kd((long)k, (long)d) &&
+         nlp_lds_bytes(64, (int)k, (int)d) <= GEOM_LDS_MAX &&
+         nlp_lds_bytes(128, (int)k, (int)d) <= GEOM_LDS_MAX;
+}
+
+int64_t fused_expert_nll_panel_scratch_bytes(int64_t grid, int64_t k,
+                                             int64_t sb) {
+  if (sb == 0) sb = nlp_sb_default((long)k);
+  TORCH_CHECK(nlp_sb_ok(sb), "sb must be 64 or 128 (0: default), got ", sb);
+  TORCH_CHECK(k >= 1 && k <= NLP_K_MAX && grid >= 0, "k must be in [1, ",
+              NLP_K_MAX, "] and grid >= 0, got k = ", k, ", grid = ", grid);
+  return (int64_t)(nlp_scratch_floats((long)grid, (int)k, (int)sb) *
+                   sizeof(float));
+}
+
+std::vector<torch::Tensor> fused_expert_nll_panel(
+    torch::Tensor X, torch::Tensor y, torch::Tensor scale, double amp,
+    double noise, int64_t family, int64_t max_blocks, int64_t sb) {
+  check_family(family);
+  check_arg(X, "X", F32, {ANY, ANY, ANY}, true);
+  const int E = X.size(0), k = X.size(1), d = X.size(2);
+  check_arg(y, "y", F32, {E, k});
+  check_vec(scale, "scale", F32, d);
+  TORCH_CHECK(fused_expert_nll_panel_supported(k, d), "X must be [E, k, d] "
+              "with 128 < k <= 1024, 1 <= d <= 128 for "
+              "fused_expert_nll_panel, got ", X.sizes());
+  TORCH_CHECK(max_blocks >= 0, "max_blocks must be >= 0 (0: no cap), got ",
+              max_blocks);
+  if (sb == 0) sb = nlp_sb_default(k);
+  TORCH_CHECK(nlp_sb_ok(sb), "sb must be 64 or 128 (0: default), got ", sb);
+  check_same_gpu({{&X, "X"}, {&y, "y"}, {&scale, "scale"}});
+  make_contiguous({&y, &scale});
+  auto nll = torch::empty({E}, like(X, F64));
+  auto sumW0 = torch::empty_like(nll), trG = torch::empty_like(nll);
+  auto contr = torch::empty({E, d}, like(X, F64));
+  auto bad = torch::empty({E}, like(X, I32));
+  if (E == 0) return {nll, sumW0, trG, contr, bad};
+  int cus = 0, wgs = 0;
+  check_hip(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount,
+                                  X.get_device()),
+            "fused_expert_nll_panel: compute unit count");
+  check_hip(fused_expert_nll_panel_resident_wgs(k, d, (int)family, (int)sb,
+                                                &wgs),
+            "fused_expert_nll_panel: occupancy");
+  TORCH_CHECK(cus >= 1 && wgs >= 1, "fused_expert_nll_panel: the device "
+              "keeps no workgroup resident at (k, d) = (", k, ", ", d, ")");
+  const long grid = nlp_grid(E, (long)cus * wgs, (long)max_blocks, k,
+                             (int)sb);
+  const size_t floats = nlp_scratch_floats(grid, k, (int)sb);
+  TORCH_CHECK(grid >= 1 && floats * sizeof(float) <= NLP_SCRATCH_MAX_BYTES,
+              "fused_expert_nll_panel: scratch of ", floats * sizeof(float),
+              " bytes for ", grid, " workgroups is outside the limit of ",
+              NLP_SCRATCH_MAX_BYTES);
+  // every element a phase reads has been written by an earlier phase of the
+  // same expert: no clearing
+  auto scratch = torch::empty({(int64_t)floats}, like(X, F32));
+  check_hip(launch_fused_expert_nll_panel(
+                X.data_ptr<float>(), y.data_ptr<float>(),
+                scale.data_ptr<float>(), (float)amp, (float)noise, E, k, d,
+                scratch.data_ptr<float>(), (int)grid, (int)sb,
+                nll.data_ptr<double>(), sumW0.data_ptr<double>(),
+                trG.data_ptr<double>(), contr.data_ptr<double>(),
+                bad.data_ptr<int>(), (int)family, current_stream()),
+            "fused_expert_nll_panel");
+  return {nll, sumW0, trG, contr, bad};
+}
+
 // The elementwise tile (q by differences, then the family's Kb) in both of
 // its uses.  want_cm: write the
 // [c, m] copies (hi, and lo with hilo); want_t: write the transposed hi/lo
@@ -889,6 +965,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("fused_expert_nll_occupancy", &fused_expert_nll_occupancy,
           "resident workgroups per CU of the expert kernel at (k, d)",
           pybind11::arg("k"), pybind11::arg("d"), pybind11::arg("family") = (int)GEOM_FAM_RBF);
+  mod.def("fused_expert_nll_panel", &fused_expert_nll_panel,
+          "fused per-expert nll+gradient primitives for 128 < k <= 1024: "
+          "the matrix in a global scratch, tiled through LDS (CDNA4)",
+          pybind11::arg("X"), pybind11::arg("y"), pybind11::arg("scale"), pybind11::arg("amp"), pybind11::arg("noise"),
+          pybind11::arg("family") = (int)GEOM_FAM_RBF,
+          pybind11::arg("max_blocks") = 0, pybind11::arg("sb") = 0);
+  mod.def("fused_expert_nll_panel_supported",
+          &fused_expert_nll_panel_supported);
+  mod.def("fused_expert_nll_panel_scratch_bytes",
+          &fused_expert_nll_panel_scratch_bytes,
+          "bytes of the scratch of a launch of `grid` workgroups",
+          pybind11::arg("grid"), pybind11::arg("k"), pybind11::arg("sb") = 0);
   mod.def("cross_mfma_ppa", &cross_mfma_ppa,
           "MFMA sqdist cross tile + fused K^T y (K1 plan, CDNA4)",
           pybind11::arg("Xs"), pybind11::arg("As"), pybind11::arg("nx"), pybind11::arg("na"), pybind11::arg("amp"), pybind11::arg("y"),

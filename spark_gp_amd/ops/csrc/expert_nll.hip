@@ -73,7 +73,8 @@
 // whose fp32 Cholesky breaks down are flagged in out_bad and recomputed on
 // the torch fallback path by the host.
 //
-// Constraints: k <= 128, d <= 128, LDS budget checked host-side.
+// Constraints: k <= 128, d <= 128, LDS budget checked host-side.  Experts of
+// 128 < k <= 1024 rows: expert_nll_panel.hip (opt-in).
 
 #include <hip/hip_runtime.h>
 #include <math.h>

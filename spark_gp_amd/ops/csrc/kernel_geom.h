@@ -1,6 +1,7 @@
 // Kernel geometry shared by the device code and the host-side gates: the
 // LDS budgets of the fused expert kernels and the SYRK tile constants.
-// Included by expert_nll.hip, laplace.hip, cross_syrk.hip, predict.hip,
+// Included by expert_nll.hip, expert_nll_panel.hip, laplace.hip,
+// cross_syrk.hip, predict.hip,
 // predict_wide.hip, greedy.hip, kmeans.hip (hipcc) and by
 // bindings.cpp (host compiler), so a *_supported() answer and the launch it
 // guards are computed by the same function.
@@ -145,6 +146,91 @@ static GEOM_HD inline size_t lap_lds_bytes(int k, int d, int ev = 0) {
 }
 
 #define GEOM_LDS_MAX (160 * 1024)   // LDS per workgroup on gfx950
+
+// ---- panel expert kernel (expert_nll_panel.hip) ---------------------------
+// For experts past the resident kernel's LDS plan: persistent workgroups, the
+// kp x kp matrix of the expert a workgroup is on in its slab of a global
+// scratch [grid, kp, kp] (kp: k up to whole super-blocks of sb rows, the
+// padding an identity), every phase a sequence of sb x sb block products
+// whose operands pass through LDS NLP_KC contraction indices at a time.
+#define NLP_K_MIN 129
+#define NLP_K_MAX 1024
+#define NLP_D_MAX 128
+#define NLP_KC 32                 // contraction depth of a staged chunk
+// chunk row stride, = 2 (mod 4): 32 distinct banks per 32-lane group of a
+// fragment read (pp_cstr's argument)
+#define NLP_KS (NLP_KC + 2)
+#define NLP_WT 64                 // tile edge of the elementwise phase W
+// the scratch of one launch stays under this many bytes (the grid is cut to
+// fit): 256 slabs at k = 1024
+#define NLP_SCRATCH_MAX_BYTES ((size_t)1 << 30)
+
+static GEOM_HD inline bool nlp_sb_ok(long sb) { return sb == 64 || sb == 128; }
+
+// super-block rows where the caller names none.  Measured at d = 32 over 1M
+// rows (profiles/PROFILES.md round 17): 64 is 4 % faster at k = 256, 128 is
+// 8 % faster at k = 512 and 17 % at k = 1000 (half the staged bytes per
+// flop).  Between 256 and 512 the rule is not measured.
+static GEOM_HD inline int nlp_sb_default(long k) { return k <= 256 ? 64 : 128; }
+
+static GEOM_HD inline bool nlp_supported_kd(long k, long d) {
+  return k >= NLP_K_MIN && k <= NLP_K_MAX && d >= 1 && d <= NLP_D_MAX;
+}
+
+static GEOM_HD inline int nlp_kp(int k, int sb) {
+  return (k + sb - 1) / sb * sb;
+}
+
+// floats of the block buffer: the leaf's sb x (sb + 4) diagonal block, or
+// phase W's transposed tile
+static GEOM_HD inline size_t nlp_pbuf_floats(int sb) {
+  const size_t p = (size_t)sb * geom_sa(sb), w = NLP_WT * (NLP_WT + 1);
+  return p > w ? p : w;
+}
+
+// chol_invert_lower's temp for an sb-row block
+static GEOM_HD inline size_t nlp_tsz(int sb) {
+  const size_t t = (size_t)(sb - 32) * 36;
+  return t > 448 ? t : 448;
+}
+
+// LDS bytes of fused_expert_nll_panel_kernel; region order is its carve
+static GEOM_HD inline size_t nlp_lds_bytes(int sb, int k, int d) {
+  const int kp = nlp_kp(k, sb);
+  size_t off = 0;
+  off += a16(sizeof(double) * 10);                       // red + misc
+  off += a16(sizeof(double) * NLP_D_MAX);                // hs
+  off += a16(sizeof(float) * nlp_pbuf_floats(sb));       // P
+  off += a16(sizeof(float) * nlp_tsz(sb));               // T
+  off += 2 * a16(sizeof(float) * (size_t)sb * NLP_KS);   // As Bs
+  off += a16(sizeof(float) * (size_t)(sb / 16) * sb);    // Hp
+  off += 5 * a16(sizeof(float) * kp);          // yb alpha tvec rrow nrm
+  off += 2 * a16(sizeof(float) * d);                     // sc s2
+  off += 16;                                             // bad (+pad)
+  return off;
+}
+
+static GEOM_HD inline size_t nlp_slab_floats(int k, int sb) {
+  return (size_t)nlp_kp(k, sb) * (size_t)nlp_kp(k, sb);
+}
+
+// workgroups of one launch over E experts: at most what the device keeps
+// resident, what NLP_SCRATCH_MAX_BYTES holds, and max_blocks if > 0
+static GEOM_HD inline long nlp_grid(long E, long resident, long max_blocks,
+                                    int k, int sb) {
+  long g = E;
+  if (g > resident) g = resident;
+  const long fit = (long)(NLP_SCRATCH_MAX_BYTES /
+                          (nlp_slab_floats(k, sb) * sizeof(float)));
+  if (g > fit) g = fit;
+  if (max_blocks > 0 && g > max_blocks) g = max_blocks;
+  return g;
+}
+
+// floats of the scratch of a launch of `grid` workgroups: never grows with E
+static GEOM_HD inline size_t nlp_scratch_floats(long grid, int k, int sb) {
+  return (size_t)grid * nlp_slab_floats(k, sb);
+}
 
 // ---- fused prediction (predict.hip) ---------------------------------------
 // One block owns a tile of TR test rows and keeps their whole fp32 cross

@@ -23,6 +23,19 @@ hipError_t launch_fused_expert_nll(
 
 hipError_t fused_expert_nll_resident_wgs(int k, int d, int family, int* out);
 
+// ---- expert_nll_panel.hip -------------------------------------------------
+// 128 < k <= 1024 (nlp_supported_kd).  scratch: nlp_scratch_floats(grid, k,
+// sb) floats for 1 <= grid <= E persistent workgroups; sb: the super-block,
+// 64 or 128.  An unknown sb is answered like an unknown family.
+hipError_t launch_fused_expert_nll_panel(
+    const float* X, const float* y, const float* scale, float amp,
+    float noise, int E, int k, int d, float* scratch, int grid, int sb,
+    double* out_nll, double* out_sumW0, double* out_trG, double* out_contr,
+    int* out_bad, int family, hipStream_t stream);
+
+hipError_t fused_expert_nll_panel_resident_wgs(int k, int d, int family,
+                                               int sb, int* out);
+
 // ---- laplace.hip ----------------------------------------------------------
 // (these two answer an unknown family, like an unsupported (k, d), with
 // hipErrorInvalidConfiguration)

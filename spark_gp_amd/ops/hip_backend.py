@@ -48,16 +48,27 @@ def supports_nll(cs: CompiledKernel, X: torch.Tensor) -> bool:
     return _supports_expert(cs, X, ext.fused_expert_nll_supported, BASES)
 
 
+def supports_nll_panel(cs: CompiledKernel, X: torch.Tensor) -> bool:
+    """Contiguous experts of 128 < k <= 1024 rows, d <= 128: the shapes past
+    the resident kernel's LDS plan that expert_nll_panel.hip takes."""
+    return (_supports_expert(cs, X, ext.fused_expert_nll_panel_supported,
+                             BASES) and X.is_contiguous())
+
+
 def nll_grad_compiled(cs: CompiledKernel, theta: np.ndarray,
-                      X: torch.Tensor, y: torch.Tensor
+                      X: torch.Tensor, y: torch.Tensor, panel: bool = False
                       ) -> Tuple[float, np.ndarray]:
+    """``panel``: launch ``ext.fused_expert_nll_panel`` (experts of more than
+    128 rows) instead of ``ext.fused_expert_nll``; the two return the same
+    five arrays and everything behind the launch is shared."""
     E, k, d = X.shape
     C = cs.amp(theta)
     nu = cs.noise(theta)
     s = base_scale(cs.base, theta[cs.base_idx], d)
     scale = torch.as_tensor(s, dtype=torch.float32, device=X.device)
     # sumW0 = sum(G o Kb), contr_j = sum_ab (G o Kd)_ab (x_aj - x_bj)^2
-    nll, sumW0, trG, contr, bad = ext.fused_expert_nll(
+    entry = ext.fused_expert_nll_panel if panel else ext.fused_expert_nll
+    nll, sumW0, trG, contr, bad = entry(
         X, y.to(torch.float32), scale, float(C), float(nu),
         family=base_family(cs.base))
 
