@@ -84,6 +84,7 @@ class GaussianProcessParams:
         "device": "_device",
         "dtype": "_dtype",
         "ppa_precision": "_ppa_precision",
+        "fused_ppa_fp64": "_fused_ppa_fp64",
         "optimizer_restart": "_optimizer_restart",
     }
 
@@ -100,6 +101,7 @@ class GaussianProcessParams:
         self._dtype: Optional[torch.dtype] = None  # None -> f64 CPU / f32 GPU
         self._ppa_precision = "fp64"  # 'fp64' (reference-parity) | 'mixed'
                                       # (hi/lo bf16 MFMA SYRK, fastest)
+        self._fused_ppa_fp64 = False  # 'fp64' on the f64 matrix cores
         self._optimizer_restart = True  # restart-on-bound-collapse guard
         self.model_ = None            # last fitted model (sklearn interop)
         if params:
@@ -194,6 +196,14 @@ class GaussianProcessParams:
         if p not in ("fp64", "mixed"):
             raise ValueError("ppa precision must be 'fp64' or 'mixed'")
         self._ppa_precision = p
+        return self
+
+    def setFusedPpaFp64(self, v: bool):
+        """Run the 'fp64' PPA accumulation on the fused f64 matrix-core
+        kernel (GPU, fp32 data, active sets up to 8192): the same fp32 kernel
+        values, fp64 products and sums, no fp64 copy of K_nm.  Default False;
+        ignored with 'mixed' and on the CPU."""
+        self._fused_ppa_fp64 = bool(v)
         return self
 
     def setDtype(self, dtype: torch.dtype):
@@ -303,7 +313,8 @@ class GaussianProcessCommons(GaussianProcessParams):
         instr.log_timing("active_set", t1 - t0)
 
         KK, Ky = accumulate_ppa_stats(kernel, active, X, y, comm,
-                                      precision=self._ppa_precision)
+                                      precision=self._ppa_precision,
+                                      fused_fp64=self._fused_ppa_fp64)
         t2 = stage_clock()
         instr.log_timing("ppa_accumulate", t2 - t1)
 

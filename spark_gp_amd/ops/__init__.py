@@ -136,11 +136,17 @@ def laplace_nll_grad(kernel: Kernel, theta: np.ndarray, X: torch.Tensor,
 
 def kmn_knm_and_kmny(kernel: Kernel, active: torch.Tensor,
                      X: torch.Tensor, y: torch.Tensor,
-                     chunk_rows: int = 262144, precision: str = "fp64"):
+                     chunk_rows: int = 262144, precision: str = "fp64",
+                     fused_fp64: bool = False):
+    """``fused_fp64``: the HIP backend's fp64 branch on the f64 matrix cores
+    (opt-in; the torch backend is fp64 throughout and ignores it)."""
     hip = _backend_for("kmn_knm_and_kmny", X)
     if hip is not None and hip.supports_ppa(kernel, X):
+        if not fused_fp64:
+            return hip.kmn_knm_and_kmny(kernel, active, X, y, chunk_rows,
+                                        precision)
         return hip.kmn_knm_and_kmny(kernel, active, X, y, chunk_rows,
-                                    precision)
+                                    precision, fused_fp64=True)
     return torch_backend.kmn_knm_and_kmny(kernel, active, X, y, chunk_rows)
 
 

@@ -471,6 +471,76 @@ void ppa_fused_acc(torch::Tensor Xs, torch::Tensor As, torch::Tensor nx,
             "ppa_fused_acc");
 }
 
+// Fused fp64 PPA accumulation (ppa_fp64.hip): KK [m, m] += K^T K and
+// Ky [m] += K^T y with fp32 kernel values and fp64 products and sums, both
+// triangles of KK written, the same bits on every run.
+//
+// With A (and s2): X is the fp32 rows [c, d], d <= PF_DMAX, and the blocks
+// generate K = amp Kb(sum_j s2_j (x_j - a_j)^2) themselves.  Without: X is
+// the fp32 chunk K [c, m] (cross_kernel_tile's output) and s2, amp and
+// family are not used.
+//
+// partials: scratch of ppa_fp64_partials_numel(m, split_k) doubles or more,
+// contents irrelevant; allocated here when absent and needed (split_k > 1).
+bool ppa_fp64_supported(int64_t m, int64_t d) {
+  return ppa_fp64_supported_md(m, d);
+}
+
+void ppa_fp64_acc(torch::Tensor X, torch::Tensor y, torch::Tensor Ky,
+                  torch::Tensor KK, int64_t split_k,
+                  c10::optional<torch::Tensor> A,
+                  c10::optional<torch::Tensor> s2, double amp, int64_t family,
+                  c10::optional<torch::Tensor> partials) {
+  check_family(family);
+  check_arg(X, "X", F32, {ANY, ANY});
+  const bool gen = A.has_value();
+  TORCH_CHECK(gen == s2.has_value(), "A and s2 come together");
+  if (gen) {
+    check_arg(*A, "A", F32, {ANY, X.size(1)});
+    check_vec(*s2, "s2", F32, X.size(1));
+  }
+  const int64_t c = X.size(0), m = gen ? A->size(0) : X.size(1);
+  const int64_t d = gen ? X.size(1) : 1;
+  TORCH_CHECK(ppa_fp64_supported(m, d) && (!gen || d <= PF_DMAX),
+              "X: unsupported (m, d) = (", m, ", ", d, ") for ppa_fp64_acc; "
+              "query ppa_fp64_supported, and generate for d <= ", PF_DMAX);
+  TORCH_CHECK(c <= (1 << 30), "X: at most 2^30 rows per call, got ", c);
+  check_vec(y, "y", F32, c);
+  check_vec(Ky, "Ky", F64, m, true);
+  check_arg(KK, "KK", F64, {m, m}, true);
+  TORCH_CHECK(split_k >= 1 && split_k * pf_tiles(m) <= INT_MAX,
+              "split_k out of range [1, ", INT_MAX / pf_tiles(m), "]: ",
+              split_k);
+  const int64_t part_doubles = (int64_t)pf_partial_doubles(m, split_k);
+  if (partials.has_value()) {
+    check_dtype(*partials, "partials", F64, true);
+    TORCH_CHECK(partials->numel() >= part_doubles, "partials must have at "
+                "least ", part_doubles, " elements for this (m, split_k), "
+                "got ", partials->numel());
+  }
+  check_same_gpu({{&X, "X"}, {&y, "y"}, {&Ky, "Ky"}, {&KK, "KK"},
+                  {gen ? &*A : nullptr, "A"}, {gen ? &*s2 : nullptr, "s2"},
+                  {partials.has_value() ? &*partials : nullptr, "partials"}});
+  if (c == 0) return;
+  torch::Tensor part = partials.has_value()
+                           ? *partials
+                           : torch::empty({part_doubles}, like(KK, F64));
+  torch::Tensor Ac, s2c;
+  make_contiguous({&X, &y});
+  if (gen) {
+    Ac = A->contiguous();
+    s2c = s2->contiguous();
+  }
+  check_hip(launch_ppa_fp64(
+                X.data_ptr<float>(), gen ? Ac.data_ptr<float>() : nullptr,
+                gen ? s2c.data_ptr<float>() : nullptr, (float)amp,
+                y.data_ptr<float>(), (int)c, (int)m, (int)d, (int)split_k,
+                Ky.data_ptr<double>(), KK.data_ptr<double>(),
+                part_doubles ? part.data_ptr<double>() : nullptr,
+                (int)family, current_stream()),
+            "ppa_fp64_acc");
+}
+
 void colsum_gemv_acc(torch::Tensor Kc, torch::Tensor y, torch::Tensor Ky) {
   check_arg(Kc, "Kc", BF16, {ANY, ANY});
   const int c = Kc.size(0), m = Kc.size(1);
@@ -996,6 +1066,27 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
           "fp32 elements of ppa_fused_acc's partials buffer",
           pybind11::arg("c"), pybind11::arg("m"), pybind11::arg("split_k"));
   mod.def("ppa_fused_supported", &ppa_fused_supported);
+  mod.attr("PF_TILE") = (int)PF_TILE;
+  mod.attr("PF_BK") = (int)PF_BK;
+  mod.attr("PF_DMAX") = (int)PF_DMAX;
+  mod.attr("PF_M_MAX") = (int)PF_M_MAX;
+  mod.def("ppa_fp64_acc", &ppa_fp64_acc,
+          "KK += K^T K, Ky += K^T y in fp64 on the f64 matrix cores; K "
+          "generated from (X, A, s2) or read from the fp32 chunk X (CDNA4)",
+          pybind11::arg("X"), pybind11::arg("y"), pybind11::arg("Ky"),
+          pybind11::arg("KK"), pybind11::arg("split_k"),
+          pybind11::arg("A") = pybind11::none(),
+          pybind11::arg("s2") = pybind11::none(),
+          pybind11::arg("amp") = 1.0,
+          pybind11::arg("family") = (int)GEOM_FAM_RBF,
+          pybind11::arg("partials") = pybind11::none());
+  mod.def("ppa_fp64_partials_numel",
+          [](int64_t m, int64_t split_k) {
+            return (int64_t)pf_partial_doubles(m, split_k);
+          },
+          "fp64 elements of ppa_fp64_acc's partials buffer",
+          pybind11::arg("m"), pybind11::arg("split_k"));
+  mod.def("ppa_fp64_supported", &ppa_fp64_supported);
   mod.def("cross_kernel_tile_ppa", &cross_kernel_tile_ppa,
           "transposed hi/lo tiles + fused K^T y accumulation (CDNA4)",
           pybind11::arg("X"), pybind11::arg("A"), pybind11::arg("s2v"), pybind11::arg("amp"), pybind11::arg("y"), pybind11::arg("Ky"),

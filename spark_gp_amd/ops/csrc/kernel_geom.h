@@ -2,7 +2,7 @@
 // LDS budgets of the fused expert kernels and the SYRK tile constants.
 // Included by expert_nll.hip, expert_nll_panel.hip, laplace.hip,
 // cross_syrk.hip, predict.hip,
-// predict_wide.hip, greedy.hip, kmeans.hip (hipcc) and by
+// predict_wide.hip, greedy.hip, kmeans.hip, ppa_fp64.hip (hipcc) and by
 // bindings.cpp (host compiler), so a *_supported() answer and the launch it
 // guards are computed by the same function.
 #pragma once
@@ -500,3 +500,39 @@ static GEOM_HD inline size_t sf_partial_floats(long c, long m, long split_k) {
 // largest lower-triangle tile set the split-k family (syrk_bf16,
 // syrk_fused_gen) takes; larger sets go to the k-synchronized kernel
 #define SY_SPLITK_MAX_TILES 256
+
+// ---- fp64 PPA accumulation (ppa_fp64.hip) ---------------------------------
+// KK += K^T K on the f64 matrix cores: a block owns one PF_TILE x PF_TILE
+// tile of the lower triangle and one of split_k row slices, and walks its
+// rows PF_BK at a time through two [PF_BK, PF_TILE] fp64 operand windows.
+#define PF_THREADS 256   // 2 x 2 waves, 64 x 64 outputs each
+#define PF_TILE 128
+#define PF_BK 32
+#define PF_DMAX 32       // generating feeder: dims of the A windows in LDS
+#define PF_XSTR (PF_DMAX + 1)   // their row stride: bank = row + q (mod 32)
+#define PF_M_MAX 8192    // the bound of big_chol, which consumes KK
+
+static GEOM_HD inline long pf_windows(long m) {
+  return (m + PF_TILE - 1) / PF_TILE;
+}
+
+// lower-triangle tiles, diagonal included
+static GEOM_HD inline long pf_tiles(long m) {
+  return pf_windows(m) * (pf_windows(m) + 1) / 2;
+}
+
+// doubles one row slice leaves in the partials: a full tile per output tile,
+// then PF_TILE column sums (Ky) per window
+static GEOM_HD inline size_t pf_slice_doubles(long m) {
+  return (size_t)pf_tiles(m) * PF_TILE * PF_TILE +
+         (size_t)pf_windows(m) * PF_TILE;
+}
+
+// doubles of the partials of a launch; split_k = 1 adds into KK itself
+static GEOM_HD inline size_t pf_partial_doubles(long m, long split_k) {
+  return split_k > 1 ? (size_t)split_k * pf_slice_doubles(m) : 0;
+}
+
+static GEOM_HD inline bool ppa_fp64_supported_md(long m, long d) {
+  return m >= 1 && m <= PF_M_MAX && d >= 1 && d <= 65536;
+}

@@ -82,6 +82,16 @@ hipError_t launch_syrk_fused_gen(
 hipError_t launch_colsum_gemv(const void* Kc, const float* y, int c, int m,
                               double* Ky, hipStream_t stream);
 
+// ---- ppa_fp64.hip ---------------------------------------------------------
+// KK [m, m] += K^T K and Ky [m] += K^T y in fp64, m <= PF_M_MAX.  A given:
+// K is generated from the rows X [c, d], d <= PF_DMAX; A == nullptr: X is
+// the fp32 chunk K [c, m] itself.  partials: pf_partial_doubles(m, split_k)
+// doubles of scratch (none at split_k = 1).
+hipError_t launch_ppa_fp64(
+    const float* X, const float* A, const float* s2v, float amp,
+    const float* yv, int c, int m, int d, int split_k, double* Ky, double* KK,
+    double* partials, int family, hipStream_t stream);
+
 // ---- predict.hip ----------------------------------------------------------
 // var == nullptr: mean only (M is then not read)
 hipError_t launch_ppa_predict(

@@ -215,8 +215,12 @@ def _syrk_sync_tiles(m: int, device):
 
 def kmn_knm_and_kmny(kernel: Kernel, active: torch.Tensor,
                      X: torch.Tensor, y: torch.Tensor,
-                     chunk_rows: int = 262144, precision: str = "fp64"
+                     chunk_rows: int = 262144, precision: str = "fp64",
+                     fused_fp64: bool = False
                      ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``fused_fp64``: with ``precision="fp64"``, products and sums on the
+    f64 matrix cores (ppa_fp64.hip) instead of a ``.double()`` copy and two
+    torch products per chunk; ignored with ``"mixed"``."""
     cs = compile_kernel(kernel)
     theta = kernel.get_hyperparameters()
     n, d = X.shape
@@ -232,6 +236,24 @@ def kmn_knm_and_kmny(kernel: Kernel, active: torch.Tensor,
         # reference-parity numerics: K_nm values from the HIP cross kernel
         # (fp32, ~6e-8 quantization), products and accumulation in fp64
         KK64 = torch.zeros(m, m, dtype=torch.float64, device=X.device)
+        if fused_fp64:
+            # the same fp32 K values (direct differences), widened inside
+            # the kernel; no fp64 copy, and for d <= 32 no [chunk, m] array
+            plan = ppa_plan.ppa_fp64_plan(m, d, X.dtype, chunk_rows)
+            partials = torch.empty(plan.partials_numel, dtype=torch.float64,
+                                   device=X.device)
+            for s in range(0, n, chunk_rows):
+                e = min(n, s + chunk_rows)
+                if plan.feeder == "generate":
+                    ext.ppa_fp64_acc(X[s:e], y32[s:e], Ky, KK64, plan.split_k,
+                                     A=act32, s2=s2, amp=C, family=fam,
+                                     partials=partials)
+                    continue
+                Kc = ext.cross_kernel_tile(X[s:e].contiguous(), act32, s2, C,
+                                           False, False, False, family=fam)[0]
+                ext.ppa_fp64_acc(Kc, y32[s:e], Ky, KK64, plan.split_k,
+                                 partials=partials)
+            return KK64, Ky
         for s in range(0, n, chunk_rows):
             e = min(n, s + chunk_rows)
             Kc = ext.cross_kernel_tile(X[s:e].contiguous(), act32, s2, C,

@@ -1,6 +1,7 @@
 """Host-side plan of the mixed-precision PPA accumulation (KK += K^T K,
 Ky += K^T y): which K_nm generator and SYRK kernel run, with what split-k,
-chunk length and tile lists.
+chunk length and tile lists; and of the opt-in fused fp64 accumulation
+(``ppa_fp64_plan``): its feeder, split-k and scratch size.
 
 Pure functions of ``(m, d, dtype)`` and the environment switches, free of
 the extension import so they can be tested without a device.  The constants
@@ -160,6 +161,59 @@ def ppa_plan(m: int, d: int, dtype, chunk_rows: int) -> PpaPlan:
             and _env_on("SPARK_GP_AMD_SYRK_SYNC")):
         return PpaPlan(generator, "sync", None, chunk_rows)
     return PpaPlan(generator, "splitk", syrk_staged_split_k(m), chunk_rows)
+
+
+# ---- fused fp64 accumulation (csrc/ppa_fp64.hip) ---------------------------
+FP64_TILE = 128       # output tile edge (PF_TILE)
+FP64_BK = 32          # rows per k-step (PF_BK)
+FP64_MAX_D = 32       # the generating feeder's A windows hold 32 dims (PF_DMAX)
+FP64_MAX_M = 8192     # the bound of big_chol, which consumes KK (PF_M_MAX)
+N_CU = 256            # compute units of an MI355X
+
+
+def ppa_fp64_tile_count(m: int) -> int:
+    """Lower-triangle 128 x 128 tiles of KK, diagonal included."""
+    nwin = (m + FP64_TILE - 1) // FP64_TILE
+    return nwin * (nwin + 1) // 2
+
+
+def ppa_fp64_gate(m: int, d: int, dtype) -> bool:
+    return dtype == torch.float32 and 1 <= m <= FP64_MAX_M and d >= 1
+
+
+def ppa_fp64_partials_numel(m: int, split_k: int) -> int:
+    """fp64 elements of the partials buffer: per slice a full tile per output
+    tile and 128 column sums per window; none at split_k = 1, where the
+    blocks add into KK and Ky themselves."""
+    if split_k <= 1:
+        return 0
+    nwin = (m + FP64_TILE - 1) // FP64_TILE
+    return split_k * (ppa_fp64_tile_count(m) * FP64_TILE * FP64_TILE
+                      + nwin * FP64_TILE)
+
+
+@dataclass(frozen=True)
+class PpaFp64Plan:
+    feeder: str                 # "generate" (d <= 32) | "staged"
+    split_k: int
+    partials_numel: int
+
+
+def ppa_fp64_plan(m: int, d: int, dtype, chunk_rows: int) -> PpaFp64Plan:
+    """The fused fp64 accumulation of one chunk of up to ``chunk_rows`` rows.
+    ``generate``: the blocks form K from X, the active set and s2; ``staged``:
+    they read the fp32 chunk cross_kernel_tile wrote.  split_k fills the
+    compute units once with whole blocks (a block is one tile of one row
+    slice) and is 1 when the tiles alone do; no slice is left without a
+    k-step of a full chunk."""
+    if not ppa_fp64_gate(m, d, dtype):
+        raise ValueError(f"the fused fp64 PPA accumulation takes float32 "
+                         f"inputs with 1 <= m <= {FP64_MAX_M}; got m = {m}, "
+                         f"d = {d}, {dtype}")
+    ksteps = max(1, (chunk_rows + FP64_BK - 1) // FP64_BK)
+    split_k = max(1, min(N_CU // ppa_fp64_tile_count(m), ksteps))
+    return PpaFp64Plan("generate" if d <= FP64_MAX_D else "staged", split_k,
+                       ppa_fp64_partials_numel(m, split_k))
 
 
 def syrk_sync_patch() -> Tuple[int, int]:

@@ -34,9 +34,12 @@ class NotPositiveDefiniteError(RuntimeError):
 
 def accumulate_ppa_stats(kernel: Kernel, active: torch.Tensor,
                          X: torch.Tensor, y: torch.Tensor,
-                         comm: Comm, precision: str = "fp64"
+                         comm: Comm, precision: str = "fp64",
+                         fused_fp64: bool = False
                          ) -> Tuple[torch.Tensor, torch.Tensor]:
-    KK, Ky = ops.kmn_knm_and_kmny(kernel, active, X, y, precision=precision)
+    kw = {"fused_fp64": True} if fused_fp64 else {}
+    KK, Ky = ops.kmn_knm_and_kmny(kernel, active, X, y, precision=precision,
+                                  **kw)
     comm.allreduce_(KK)
     comm.allreduce_(Ky)
     return KK, Ky
