@@ -24,6 +24,7 @@ ext = CUDAExtension(
         "spark_gp_amd/ops/csrc/expert_nll_m32.hip",
         "spark_gp_amd/ops/csrc/expert_nll_m52.hip",
         "spark_gp_amd/ops/csrc/expert_nll_panel.hip",
+        "spark_gp_amd/ops/csrc/expert_nll_f64.hip",
         "spark_gp_amd/ops/csrc/cross_syrk.hip",
         "spark_gp_amd/ops/csrc/ppa_fp64.hip",
         "spark_gp_amd/ops/csrc/laplace.hip",

@@ -29,11 +29,23 @@ from .predictor import GaussianProjectedProcessRawPredictor
 
 class GaussianProcessRegression(GaussianProcessCommons):
     _PARAMS = dict(GaussianProcessCommons._PARAMS,
-                   fused_large_experts="_fused_large_experts")
+                   fused_large_experts="_fused_large_experts",
+                   fused_fp64_experts="_fused_fp64_experts")
 
     def __init__(self, **params):
         self._fused_large_experts = False
+        self._fused_fp64_experts = False
         super().__init__(**params)
+
+    def setFusedFp64Experts(self, v: bool):
+        """Opt in to the full-fp64 fused HIP expert kernel (experts of up to
+        128 rows, d <= 128, on the GPU): every evaluation of the objective is
+        the fp64 objective of the training rows, fp32 (the GPU default; the
+        PPA stage is unchanged) or ``setDtype(torch.float64)``.  Default
+        False: fp32 rows take the fp32 fused kernel and fp64 rows the batched
+        torch objective, as before."""
+        self._fused_fp64_experts = bool(v)
+        return self
 
     def setFusedLargeExperts(self, v: bool):
         """Opt in to the fused HIP panel kernel for experts of more than 128
@@ -59,7 +71,8 @@ class GaussianProcessRegression(GaussianProcessCommons):
             for _, Xg, yg in groups:
                 if cs is not None:
                     nll, grad = ops.nll_grad_compiled(
-                        cs, theta, Xg, yg, panel=self._fused_large_experts)
+                        cs, theta, Xg, yg, panel=self._fused_large_experts,
+                        fused_fp64=self._fused_fp64_experts)
                 else:
                     nll, grad = ops.nll_grad_generic(kernel, theta, Xg, yg)
                 nll_total += nll

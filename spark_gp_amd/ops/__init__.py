@@ -66,14 +66,21 @@ def _backend_for(what: str, t: torch.Tensor, required: bool = True):
 
 
 def nll_grad_compiled(cs: CompiledKernel, theta: np.ndarray,
-                      X: torch.Tensor, y: torch.Tensor, panel: bool = False
-                      ) -> Tuple[float, np.ndarray]:
+                      X: torch.Tensor, y: torch.Tensor, panel: bool = False,
+                      fused_fp64: bool = False) -> Tuple[float, np.ndarray]:
     """``panel``: let experts of 128 < k <= 1024 rows (d <= 128, fp32, on
     the GPU) take the fused HIP panel kernel.  Default False: those shapes
     take the batched torch path, as before; every other input takes the
-    path it always took, whatever ``panel`` says."""
+    path it always took, whatever ``panel`` says.
+
+    ``fused_fp64``: let experts of k <= 128 rows (d <= 128, fp32 or fp64,
+    contiguous, on the GPU) take the full-fp64 fused HIP kernel: the fp64
+    objective of the rows as given.  Ignored on the CPU and where that
+    kernel's gate refuses; default False changes nothing."""
     hip = (_backend_for("nll_grad_compiled", X)
            if cs.base in BASES else None)
+    if fused_fp64 and hip is not None and hip.supports_nll_f64(cs, X):
+        return hip.nll_grad_compiled(cs, theta, X, y, f64=True)
     if hip is not None and hip.supports_nll(cs, X):
         return hip.nll_grad_compiled(cs, theta, X, y)
     if panel and hip is not None and hip.supports_nll_panel(cs, X):

@@ -235,6 +235,43 @@ std::vector<torch::Tensor> fused_expert_nll_panel(
   return {nll, sumW0, trG, contr, bad};
 }
 
+// The same five outputs in full fp64 for k <= 128, d <= 128
+// (expert_nll_f64.hip): X fp32 or fp64, widened at the load and read in
+// place (a non-contiguous X is refused, not copied); y and the scale vector
+// fp64, since an fp32 scale would cap the result at 1e-7.
+bool fused_expert_nll_f64_supported(int64_t k, int64_t d) {
+  return nllf64_supported((long)k, (long)d);
+}
+
+std::vector<torch::Tensor> fused_expert_nll_f64(
+    torch::Tensor X, torch::Tensor y, torch::Tensor scale, double amp,
+    double noise, int64_t family) {
+  check_family(family);
+  const bool x64 = X.scalar_type() == F64;
+  check_arg(X, "X", x64 ? F64 : F32, {ANY, ANY, ANY}, true);
+  const int E = X.size(0), k = X.size(1), d = X.size(2);
+  check_arg(y, "y", F64, {E, k});
+  check_vec(scale, "scale", F64, d);
+  TORCH_CHECK(fused_expert_nll_f64_supported(k, d), "X must be [E, k, d] "
+              "with 1 <= k <= 128, 1 <= d <= 128 for fused_expert_nll_f64, "
+              "got ", X.sizes());
+  check_same_gpu({{&X, "X"}, {&y, "y"}, {&scale, "scale"}});
+  make_contiguous({&y, &scale});
+  auto nll = torch::empty({E}, like(X, F64));
+  auto sumW0 = torch::empty_like(nll), trG = torch::empty_like(nll);
+  auto contr = torch::empty({E, d}, like(X, F64));
+  auto bad = torch::empty({E}, like(X, I32));
+  if (E == 0) return {nll, sumW0, trG, contr, bad};
+  check_hip(launch_fused_expert_nll_f64(
+                X.data_ptr(), x64 ? 1 : 0, y.data_ptr<double>(),
+                scale.data_ptr<double>(), amp, noise, E, k, d,
+                nll.data_ptr<double>(), sumW0.data_ptr<double>(),
+                trG.data_ptr<double>(), contr.data_ptr<double>(),
+                bad.data_ptr<int>(), (int)family, current_stream()),
+            "fused_expert_nll_f64");
+  return {nll, sumW0, trG, contr, bad};
+}
+
 // The elementwise tile (q by differences, then the family's Kb) in both of
 // its uses.  want_cm: write the
 // [c, m] copies (hi, and lo with hilo); want_t: write the transposed hi/lo
@@ -1047,6 +1084,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
           &fused_expert_nll_panel_scratch_bytes,
           "bytes of the scratch of a launch of `grid` workgroups",
           pybind11::arg("grid"), pybind11::arg("k"), pybind11::arg("sb") = 0);
+  mod.def("fused_expert_nll_f64", &fused_expert_nll_f64,
+          "fused per-expert nll+gradient primitives in full fp64 on the f64 "
+          "matrix cores, k <= 128 (CDNA4)",
+          pybind11::arg("X"), pybind11::arg("y"), pybind11::arg("scale"), pybind11::arg("amp"), pybind11::arg("noise"),
+          pybind11::arg("family") = (int)GEOM_FAM_RBF);
+  mod.def("fused_expert_nll_f64_supported", &fused_expert_nll_f64_supported);
   mod.def("cross_mfma_ppa", &cross_mfma_ppa,
           "MFMA sqdist cross tile + fused K^T y (K1 plan, CDNA4)",
           pybind11::arg("Xs"), pybind11::arg("As"), pybind11::arg("nx"), pybind11::arg("na"), pybind11::arg("amp"), pybind11::arg("y"),

@@ -1,6 +1,7 @@
 // Kernel geometry shared by the device code and the host-side gates: the
 // LDS budgets of the fused expert kernels and the SYRK tile constants.
-// Included by expert_nll.hip, expert_nll_panel.hip, laplace.hip,
+// Included by expert_nll.hip, expert_nll_panel.hip, expert_nll_f64.hip,
+// laplace.hip,
 // cross_syrk.hip, predict.hip,
 // predict_wide.hip, greedy.hip, kmeans.hip, ppa_fp64.hip (hipcc) and by
 // bindings.cpp (host compiler), so a *_supported() answer and the launch it
@@ -146,6 +147,48 @@ static GEOM_HD inline size_t lap_lds_bytes(int k, int d, int ev = 0) {
 }
 
 #define GEOM_LDS_MAX (160 * 1024)   // LDS per workgroup on gfx950
+
+// ---- fp64 expert kernel (expert_nll_f64.hip) ------------------------------
+// The whole kp x kp fp64 matrix of an expert in LDS (kp: k up to whole
+// 16-row MFMA tiles, the padding an identity), factored by 16-column blocks.
+#define NLF_K_MAX 128
+#define NLF_D_MAX 128
+#define NLF_TB 16                 // block width = the 16x16x4 f64 MFMA tile
+#define NLF_XC 16                 // feature columns of a staged slab of x'
+// slab row stride in doubles, = 2 (mod 4) like nllf64_sa: the 16-row by
+// 2-column fragment read of a 32-lane group covers the 64 banks once
+#define NLF_XS (NLF_XC + 2)
+
+static GEOM_HD inline int nllf64_kp(int k) {
+  return (k + NLF_TB - 1) / NLF_TB * NLF_TB;
+}
+
+// row stride of the matrix in doubles: kp + 2 = 2 (mod 4)
+static GEOM_HD inline int nllf64_sa(int k) {
+  return nllf64_kp(k) + 2;
+}
+
+// LDS bytes of fused_expert_nll_f64_kernel; region order is f64_carve's.
+// 102 KB at (100, 32), 159 840 B at (128, 128): every k <= 128, d <= 128
+// fits (the kernel's registers keep it at one workgroup per CU anyway).
+static GEOM_HD inline size_t nllf64_lds_bytes(int k, int d) {
+  const size_t kp = (size_t)nllf64_kp(k);
+  size_t off = 0;
+  off += a16(sizeof(double) * 10);                          // red
+  off += a16(sizeof(double) * kp * (size_t)nllf64_sa(k));   // A
+  off += a16(sizeof(double) * kp * NLF_XS);                 // T
+  off += a16(sizeof(double) * (NLF_K_MAX / NLF_TB) * NLF_XC);   // Hp
+  off += a16(sizeof(double) * d);                           // hs
+  off += 5 * a16(sizeof(double) * kp);         // yb alpha tvec rrow nrm
+  off += a16(sizeof(double) * d);                           // sc
+  off += 16;                                                // bad (+pad)
+  return off;
+}
+
+static GEOM_HD inline bool nllf64_supported(long k, long d) {
+  return k >= 1 && k <= NLF_K_MAX && d >= 1 && d <= NLF_D_MAX &&
+         nllf64_lds_bytes((int)k, (int)d) <= GEOM_LDS_MAX;
+}
 
 // ---- panel expert kernel (expert_nll_panel.hip) ---------------------------
 // For experts past the resident kernel's LDS plan: persistent workgroups, the

@@ -36,6 +36,15 @@ hipError_t launch_fused_expert_nll_panel(
 hipError_t fused_expert_nll_panel_resident_wgs(int k, int d, int family,
                                                int sb, int* out);
 
+// ---- expert_nll_f64.hip ---------------------------------------------------
+// The outputs of launch_fused_expert_nll in full fp64, k <= 128 and d <= 128
+// (nllf64_supported).  X: [E, k, d] floats, or doubles with x_is_f64.
+hipError_t launch_fused_expert_nll_f64(
+    const void* X, int x_is_f64, const double* y, const double* scale,
+    double amp, double noise, int E, int k, int d, double* out_nll,
+    double* out_sumW0, double* out_trG, double* out_contr, int* out_bad,
+    int family, hipStream_t stream);
+
 // ---- laplace.hip ----------------------------------------------------------
 // (these two answer an unknown family, like an unsupported (k, d), with
 // hipErrorInvalidConfiguration)

@@ -55,21 +55,36 @@ def supports_nll_panel(cs: CompiledKernel, X: torch.Tensor) -> bool:
                              BASES) and X.is_contiguous())
 
 
+def supports_nll_f64(cs: CompiledKernel, X: torch.Tensor) -> bool:
+    """Contiguous fp32 or fp64 experts of k <= 128 rows, d <= 128: what
+    expert_nll_f64.hip takes (fp32 rows are widened at the load)."""
+    if cs is None or cs.base not in BASES or X.dim() != 3:
+        return False
+    if X.dtype not in (torch.float32, torch.float64):
+        return False
+    return X.is_contiguous() and bool(
+        ext.fused_expert_nll_f64_supported(X.shape[1], X.shape[2]))
+
+
 def nll_grad_compiled(cs: CompiledKernel, theta: np.ndarray,
-                      X: torch.Tensor, y: torch.Tensor, panel: bool = False
-                      ) -> Tuple[float, np.ndarray]:
+                      X: torch.Tensor, y: torch.Tensor, panel: bool = False,
+                      f64: bool = False) -> Tuple[float, np.ndarray]:
     """``panel``: launch ``ext.fused_expert_nll_panel`` (experts of more than
-    128 rows) instead of ``ext.fused_expert_nll``; the two return the same
-    five arrays and everything behind the launch is shared."""
+    128 rows) instead of ``ext.fused_expert_nll``; ``f64``: launch
+    ``ext.fused_expert_nll_f64`` (full fp64; y and the scale go in as fp64).
+    The three return the same five arrays and everything behind the launch
+    is shared."""
     E, k, d = X.shape
     C = cs.amp(theta)
     nu = cs.noise(theta)
     s = base_scale(cs.base, theta[cs.base_idx], d)
-    scale = torch.as_tensor(s, dtype=torch.float32, device=X.device)
+    dt = torch.float64 if f64 else torch.float32
+    scale = torch.as_tensor(s, dtype=dt, device=X.device)
     # sumW0 = sum(G o Kb), contr_j = sum_ab (G o Kd)_ab (x_aj - x_bj)^2
-    entry = ext.fused_expert_nll_panel if panel else ext.fused_expert_nll
+    entry = (ext.fused_expert_nll_f64 if f64 else
+             ext.fused_expert_nll_panel if panel else ext.fused_expert_nll)
     nll, sumW0, trG, contr, bad = entry(
-        X, y.to(torch.float32), scale, float(C), float(nu),
+        X, y.to(dt), scale, float(C), float(nu),
         family=base_family(cs.base))
 
     # single device->host transfer for all reductions (one sync per eval)
@@ -91,11 +106,15 @@ def nll_grad_compiled(cs: CompiledKernel, theta: np.ndarray,
                             g_amp=-0.5 * sumW0_t, g_noise=-0.5 * trG_t)
 
     if n_bad:
-        # fp32 Cholesky broke down for these experts (huge-amplitude
-        # iterates); recompute them on the torch path (LU fallback inside)
+        # the kernel's Cholesky broke down for these experts (huge-amplitude
+        # iterates); recompute them on the torch path (LU fallback inside),
+        # under f64 in fp64 so that the rescue is no less precise
         idx = (bad != 0).nonzero(as_tuple=True)[0]
+        Xb, yb = X[idx], y[idx]
+        if f64:
+            Xb, yb = Xb.double(), yb.double()
         nll_b, grad_b = torch_backend.nll_grad_compiled(
-            cs, theta, X[idx], y[idx], force_lu=True)
+            cs, theta, Xb, yb, force_lu=True)
         nll_total += nll_b
         grad += grad_b
     return nll_total, grad
