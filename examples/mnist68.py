@@ -32,6 +32,10 @@ def main(argv=None):
                    choices=["probit", "logistic"])
     p.add_argument("--max-iter", type=int, default=100)
     p.add_argument("--device", type=str, default=None)
+    p.add_argument("--fused-wide-features", action="store_true",
+                   help="setFusedWideFeatures(True): the 784-dim experts take "
+                        "the streamed-feature HIP Laplace kernels.  Logistic "
+                        "link only; under --link probit it does nothing")
     args = p.parse_args(argv)
 
     X, y = mnist_like_binary(args.rows, seed=13)
@@ -45,7 +49,8 @@ def main(argv=None):
           .setSigma2(1e-3)
           .setTol(1e-3)
           .setMaxIter(args.max_iter)
-          .setSeed(13))
+          .setSeed(13)
+          .setFusedWideFeatures(args.fused_wide_features))
     if args.device:
         gp.setDevice(args.device)
 
@@ -54,7 +59,7 @@ def main(argv=None):
                                  metric=accuracy, seed=13)
     dt = time.perf_counter() - t0
     print(f"rows={args.rows} d=784 m={args.active_set} link={args.link} "
-          f"accuracy: {acc:.4f}  fit+eval: {dt:.2f}s")
+          f"fused_wide={args.fused_wide_features} accuracy: {acc:.4f}  fit+eval: {dt:.2f}s")
     return acc
 
 

@@ -26,12 +26,14 @@ class GaussianProcessClassifier(GaussianProcessCommons):
     _PARAMS = dict(GaussianProcessCommons._PARAMS,
                    max_newton_iter="_max_newton_iter",
                    link="_link",
-                   fused_matern="_fused_matern")
+                   fused_matern="_fused_matern",
+                   fused_wide_features="_fused_wide_features")
 
     def __init__(self, **params):
         self._max_newton_iter = 200
         self._link = "logistic"
         self._fused_matern = False
+        self._fused_wide_features = False
         super().__init__(**params)
 
     def setMaxNewtonIter(self, v: int):
@@ -54,6 +56,16 @@ class GaussianProcessClassifier(GaussianProcessCommons):
         Default False: those bases take the batched torch Newton loop, as
         before; RBF bases take the fused kernels either way."""
         self._fused_matern = bool(v)
+        return self
+
+    def setFusedWideFeatures(self, v: bool):
+        """Opt in to the streamed-feature fused HIP Laplace kernels for
+        experts with more feature dimensions than rows (d > k, up to 1024
+        dimensions and 128 rows; 'rbf' and 'ard' bases under the logistic
+        link).  Default False: those shapes take the batched torch Newton
+        loop, as before; shapes with d <= k take the resident fused kernels
+        either way."""
+        self._fused_wide_features = bool(v)
         return self
 
     def _resolve_likelihood(self):
@@ -86,7 +98,8 @@ class GaussianProcessClassifier(GaussianProcessCommons):
                 nll, grad = ops.laplace_nll_grad(
                     kernel, theta, Xg, yg, fg, self._tol,
                     self._max_newton_iter, likelihood=lik,
-                    fused_matern=self._fused_matern)
+                    fused_matern=self._fused_matern,
+                    fused_wide=self._fused_wide_features)
                 nll_total += nll
                 grad_total += grad
             return nll_total, grad_total

@@ -96,9 +96,12 @@ def nll_grad_generic(kernel: Kernel, theta: np.ndarray,
 def laplace_nll_grad(kernel: Kernel, theta: np.ndarray, X: torch.Tensor,
                      y: torch.Tensor, f: torch.Tensor, tol: float,
                      max_newton_iter: int = 200, likelihood=None,
-                     fused_matern: bool = False):
+                     fused_matern: bool = False, fused_wide: bool = False):
     """``fused_matern``: let the Matern 3/2 and 5/2 bases take the fused HIP
-    Laplace kernels as well (opt-in; the RBF bases always do)."""
+    Laplace kernels as well (opt-in; the RBF bases always do).
+    ``fused_wide``: let RBF-base experts with more feature dimensions than
+    rows (up to 1024) take the streamed-feature HIP kernels (opt-in; without
+    it those shapes run the batched torch path)."""
     from ..kernels.compiled import compile_kernel
     from ..likelihoods import LogisticLikelihood
     logistic = likelihood is None or isinstance(likelihood,
@@ -134,6 +137,19 @@ def laplace_nll_grad(kernel: Kernel, theta: np.ndarray, X: torch.Tensor,
             # than the fp32 kernel's clamp (LAPLACE_MIN_TOL): the torch
             # Newton polish continues from the warm f with the exact
             # requested tolerance (a few cheap iterations).
+            return torch_backend.laplace_nll_grad(
+                kernel, theta, X, y, f, tol, max_newton_iter)
+        if fused_wide and hip.supports_laplace_wide(cs, X):
+            # the two branches above on laplace_wide.hip, which streams X
+            # (d > k, up to 1024 dimensions)
+            if tol >= hip.LAPLACE_MIN_TOL:
+                res = hip.laplace_evidence(cs, theta, X, y, f, tol,
+                                           max_newton_iter, wide=True)
+                if res is not None:
+                    return res
+            else:
+                hip.laplace_newton(cs, theta, X, y, f, tol, max_newton_iter,
+                                   wide=True)
             return torch_backend.laplace_nll_grad(
                 kernel, theta, X, y, f, tol, max_newton_iter)
     return torch_backend.laplace_nll_grad(kernel, theta, X, y, f, tol,

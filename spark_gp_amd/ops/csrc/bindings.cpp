@@ -654,6 +654,66 @@ bool fused_laplace_evidence_supported(int64_t k, int64_t d) {
   return lap_lds_bytes((int)k, (int)d, 1) <= GEOM_LDS_MAX;
 }
 
+// The two entries above on laplace_wide.hip, which streams X instead of
+// holding it in LDS: RBF family, 1 <= k <= 128, 1 <= d <= 1024 (d > k
+// included).  Same tuples, same max_newton = 0 contract.  X must be
+// contiguous: the experts are large, and a silent copy of them per call
+// would cost more than the launch.
+bool fused_laplace_wide_supported(int64_t k, int64_t d) {
+  return lapw_supported((long)k, (long)d, 1);
+}
+
+// workgroups of the wide evidence kernel that one CU keeps resident
+int64_t fused_laplace_wide_occupancy(int64_t k, int64_t d) {
+  int wgs = 0;
+  check_hip(fused_laplace_wide_resident_wgs((int)k, (int)d, &wgs),
+            "fused_laplace_wide_occupancy");
+  return wgs;
+}
+
+template <bool EV>
+std::vector<torch::Tensor> fused_laplace_wide(
+    torch::Tensor X, torch::Tensor y, torch::Tensor f, torch::Tensor scale,
+    double amp, double noise, double tol, int64_t max_newton) {
+  const char* what =
+      EV ? "fused_laplace_evidence_wide" : "fused_laplace_newton_wide";
+  check_arg(X, "X", F32, {ANY, ANY, ANY}, true);
+  const int E = X.size(0), k = X.size(1), d = X.size(2);
+  check_arg(y, "y", F32, {E, k});
+  check_arg(f, "f", F32, {E, k}, true);   // updated in place
+  check_vec(scale, "scale", F32, d);
+  TORCH_CHECK(fused_laplace_wide_supported(k, d), "X must be [E, k, d] with "
+              "1<=k<=128, 1<=d<=", LAPW_D_MAX, " for ", what, ", got ",
+              X.sizes());
+  check_same_gpu({{&X, "X"}, {&y, "y"}, {&f, "f"}, {&scale, "scale"}});
+  make_contiguous({&y, &scale});
+  auto psi = torch::empty({E}, like(X, F64)), sll = torch::empty_like(psi);
+  auto iters = torch::empty({E}, like(X, I32)), bad = torch::empty_like(iters);
+  if (!EV) {
+    check_hip(launch_fused_laplace_newton_wide(
+                  X.data_ptr<float>(), y.data_ptr<float>(),
+                  f.data_ptr<float>(), scale.data_ptr<float>(), (float)amp,
+                  (float)noise, E, k, d, tol, (int)max_newton,
+                  psi.data_ptr<double>(), sll.data_ptr<double>(),
+                  iters.data_ptr<int>(), bad.data_ptr<int>(),
+                  current_stream()),
+              what);
+    return {psi, sll, iters, bad};
+  }
+  auto logz = torch::empty({E}, like(X, F64));
+  auto grad = torch::empty({E, d + 2}, like(X, F64));
+  check_hip(launch_fused_laplace_evidence_wide(
+                X.data_ptr<float>(), y.data_ptr<float>(),
+                f.data_ptr<float>(), scale.data_ptr<float>(), (float)amp,
+                (float)noise, E, k, d, tol, (int)max_newton,
+                psi.data_ptr<double>(), sll.data_ptr<double>(),
+                iters.data_ptr<int>(), bad.data_ptr<int>(),
+                logz.data_ptr<double>(), grad.data_ptr<double>(),
+                current_stream()),
+            what);
+  return {logz, grad, iters, bad};
+}
+
 // K14: fused prediction (predict.hip).  mean = c mv and, with want_var,
 // var = kxx + rowsum((c M) o c) for c = amp Kb(q(X, A)), without a [t, m]
 // array in memory.  M is the symmetric magic matrix; returns (mean[t] f64,
@@ -1060,6 +1120,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
           pybind11::arg("family") = (int)GEOM_FAM_RBF);
   mod.def("fused_laplace_evidence_supported",
           &fused_laplace_evidence_supported);
+  mod.def("fused_laplace_newton_wide", &fused_laplace_wide<false>,
+          "fused_laplace_newton with X streamed: d up to 1024, d > k allowed",
+          pybind11::arg("X"), pybind11::arg("y"), pybind11::arg("f"), pybind11::arg("scale"), pybind11::arg("amp"),
+          pybind11::arg("noise"), pybind11::arg("tol"), pybind11::arg("max_newton"));
+  mod.def("fused_laplace_evidence_wide", &fused_laplace_wide<true>,
+          "fused_laplace_evidence with X streamed: d up to 1024, d > k allowed",
+          pybind11::arg("X"), pybind11::arg("y"), pybind11::arg("f"), pybind11::arg("scale"), pybind11::arg("amp"),
+          pybind11::arg("noise"), pybind11::arg("tol"), pybind11::arg("max_newton"));
+  mod.def("fused_laplace_wide_supported", &fused_laplace_wide_supported);
+  mod.def("fused_laplace_wide_occupancy", &fused_laplace_wide_occupancy);
   mod.def("fused_expert_nll", &fused_expert_nll,
           "fused per-expert BCM nll+gradient primitives (CDNA4)",
           pybind11::arg("X"), pybind11::arg("y"), pybind11::arg("scale"), pybind11::arg("amp"), pybind11::arg("noise"),

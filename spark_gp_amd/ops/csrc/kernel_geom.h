@@ -148,6 +148,46 @@ static GEOM_HD inline size_t lap_lds_bytes(int k, int d, int ev = 0) {
 
 #define GEOM_LDS_MAX (160 * 1024)   // LDS per workgroup on gfx950
 
+// ---- streamed-feature Laplace kernel (laplace_wide.hip) -------------------
+// fused_laplace_kernel<ev, RBF, WIDE>: lap_lds_bytes without the k x dp4 block
+// of X and without a per-dimension region other than betav.  X passes
+// through two slab buffers of k rows by LAPW_SW columns (row stride
+// LAPW_SS = width + 4 floats: 16-B aligned rows, conflict-free fragment
+// reads); s2 is folded into the staging of the Kb cache (the scale is read
+// with the slab), and the d beta entries of gout accumulate in the output row
+// itself, so gout keeps only the amplitude and noise slots.
+//   (k, d) = (100, 784), ev: 79 248 B  -> two workgroups per CU (<= 80 KiB)
+//   (k, d) = (128, 1024), ev: 115 824 B -> one workgroup per CU
+#define LAPW_SW 16
+#define LAPW_SS (LAPW_SW + 4)
+#define LAPW_D_MAX 1024
+
+// floats of one slab buffer
+static GEOM_HD inline size_t lapw_slab_floats(int k) {
+  return a16(sizeof(float) * (size_t)k * LAPW_SS) / sizeof(float);
+}
+
+// region order is lap_carve<ev, true>'s
+static GEOM_HD inline size_t lapw_lds_bytes(int k, int d, int ev = 0) {
+  size_t off = a16(sizeof(double) * 10);
+  off += a16(sizeof(float) * (size_t)k * geom_sa(k));   // A
+  off += 2 * sizeof(float) * lapw_slab_floats(k);       // slabs
+  off += a16(sizeof(float) * geom_tsz(k));
+  off += 8 * a16(sizeof(float) * k);
+  if (ev) {
+    off += 2 * a16(sizeof(float) * k);        // vv + s2v
+    off += a16(sizeof(float) * d);            // betav
+    off += a16(sizeof(double) * 2);           // gout: amp, noise
+  }
+  off += 16;
+  return off;
+}
+
+static GEOM_HD inline bool lapw_supported(long k, long d, int ev) {
+  return k >= 1 && k <= 128 && d >= 1 && d <= LAPW_D_MAX &&
+         lapw_lds_bytes((int)k, (int)d, ev) <= GEOM_LDS_MAX;
+}
+
 // ---- fp64 expert kernel (expert_nll_f64.hip) ------------------------------
 // The whole kp x kp fp64 matrix of an expert in LDS (kp: k up to whole
 // 16-row MFMA tiles, the padding an identity), factored by 16-column blocks.

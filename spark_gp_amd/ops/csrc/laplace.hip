@@ -34,6 +34,13 @@
 // 232 VGPRs) and ran the 1M x 16 GPC fit ~1.6x slower.
 //
 // Constraints: k <= 128, d <= k; LDS budget checked host-side.
+//
+// Wide features (d > k, up to LAPW_D_MAX): fused_laplace_kernel<EV, RBF, true>,
+// compiled in laplace_wide.hip.  The Newton loop never touches X, so X need
+// not be resident: the WIDE instantiations stream it from global memory in
+// column slabs (laplace_wide.h) for the Kb cache, built on the fp32 matrix
+// cores, and for the two feature loops of the evidence tail.  Every
+// difference sits behind `if constexpr (WIDE)`.
 
 //
 // Covariance families: the kernel is fused_laplace_kernel<EV, FAM>, compiled
@@ -78,9 +85,11 @@
 #endif
 
 #include "linalg_lds.h"
+#include "laplace_wide.h"
 
 struct LapLds {
-  float* X;     // k * dp4: raw features (16-B-aligned rows)
+  float* X;     // k * dp4: raw features (16-B-aligned rows); not WIDE
+  float* slab;  // WIDE: two slab buffers of lapw_slab_floats(k)
   float* A;     // k * SA: strict upper = Kb cache (kb, no amp/noise;
                 // kb_aa = 1 implicit); lower = B -> L -> V per iteration
                 // and Binv -> W0 in the evidence tail
@@ -93,26 +102,32 @@ struct LapLds {
   float* av;    // k   a
   float* t1;    // k
   float* t2;    // k
-  float* s2;    // d
+  float* s2;    // d; not WIDE
   // evidence-mode (EV) extras
   float* vv;    // k   v = y - pi
   float* s2v;   // k   Algorithm 5.1 s2 vector
   float* betav; // d   raw base scale (beta), signed
-  double* gout; // d+2 gradient accumulators (beta..., amp, noise)
+  double* gout; // d+2 gradient accumulators (beta..., amp, noise); WIDE:
+                // amp and noise only, the beta ones are the output row
   double* red;  // 8
   double* misc; // 2
   int* bad;     // 1
 };
 
-// Region sizes: kernel_geom.h (lap_lds_bytes lists them in this order).
-template <bool EV>
+// Region sizes: kernel_geom.h (lap_lds_bytes, and lapw_lds_bytes for WIDE,
+// list them in this order).
+template <bool EV, bool WIDE>
 __device__ inline LapLds lap_carve(char* base, int k, int d) {
   LapLds L;
   char* p = base;
   L.red = (double*)p;  L.misc = L.red + 8;
   p += a16(sizeof(double) * 10);
   L.A = (float*)p;     p += a16(sizeof(float) * (size_t)k * geom_sa(k));
-  L.X = (float*)p;     p += a16(sizeof(float) * (size_t)k * geom_dp4(d));
+  if constexpr (!WIDE) {
+    L.X = (float*)p;   p += a16(sizeof(float) * (size_t)k * geom_dp4(d));
+  } else {
+    L.slab = (float*)p; p += 2 * sizeof(float) * lapw_slab_floats(k);
+  }
   L.T = (float*)p;     p += a16(sizeof(float) * geom_tsz(k));
   L.yb = (float*)p;    p += a16(sizeof(float) * k);
   L.fb = (float*)p;    p += a16(sizeof(float) * k);
@@ -122,12 +137,14 @@ __device__ inline LapLds lap_carve(char* base, int k, int d) {
   L.av = (float*)p;    p += a16(sizeof(float) * k);
   L.t1 = (float*)p;    p += a16(sizeof(float) * k);
   L.t2 = (float*)p;    p += a16(sizeof(float) * k);
-  L.s2 = (float*)p;    p += a16(sizeof(float) * d);
+  if constexpr (!WIDE) {
+    L.s2 = (float*)p;  p += a16(sizeof(float) * d);
+  }
   if (EV) {
     L.vv = (float*)p;    p += a16(sizeof(float) * k);
     L.s2v = (float*)p;   p += a16(sizeof(float) * k);
     L.betav = (float*)p; p += a16(sizeof(float) * d);
-    L.gout = (double*)p; p += a16(sizeof(double) * (d + 2));
+    L.gout = (double*)p; p += a16(sizeof(double) * (WIDE ? 2 : d + 2));
   }
   L.bad = (int*)p;
   return L;
@@ -305,13 +322,24 @@ __device__ inline void lap_trow_chunk(const float* A, const int SA,
   for (int n = 0; n < 8 * NBUF; ++n) acc[n] = lap_group_sum(acc[n]);
 }
 
+// feature j of row a: the resident block, or (WIDE) the staged slab j / 16
+template <bool WIDE>
+__device__ __forceinline__ float lap_x(const LapLds& S, const int k,
+                                       const int dp, const int a,
+                                       const int j) {
+  if constexpr (!WIDE)
+    return S.X[(size_t)a * dp + j];
+  else
+    return lapw_buf(S.slab, k, j / LAPW_SW)[a * LAPW_SS + j % LAPW_SW];
+}
+
 __device__ inline double log_sigmoid(double v) {
   // log(1/(1+exp(-v))) = -log1p(exp(-v)), stable for both signs
   if (v < -30.0) return v;
   return -log1p(exp(-v));
 }
 
-template <bool EV, int FAM>
+template <bool EV, int FAM, bool WIDE = false>
 __global__ void __launch_bounds__(WG, 4)   // 4 waves/SIMD = 2 WGs/CU
 fused_laplace_kernel(const float* __restrict__ Xg,   // [E, k, d]
                      const float* __restrict__ yg,   // [E, k]
@@ -328,9 +356,10 @@ fused_laplace_kernel(const float* __restrict__ Xg,   // [E, k, d]
                      double* __restrict__ out_grad) {   // [E,d+2] (EV)
   // the strict upper triangle caches t = sqrt(q), not Kb (header comment)
   constexpr bool TC = EV && FAM != GEOM_FAM_RBF;
+  static_assert(!WIDE || FAM == GEOM_FAM_RBF, "the streamed form is RBF's");
   extern __shared__ char lds_raw[];
   const int SA = (int)geom_sa(k);
-  LapLds S = lap_carve<EV>(lds_raw, k, d);
+  LapLds S = lap_carve<EV, WIDE>(lds_raw, k, d);
   const int e = blockIdx.x;
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -339,20 +368,26 @@ fused_laplace_kernel(const float* __restrict__ Xg,   // [E, k, d]
 
   // ---- stage X, y, f, s2 -------------------------------------------
   bool xfin = true;
+  if constexpr (!WIDE) {
   for (int i = tid; i < k * d; i += WG) {
     int a = i / d, j = i - a * d;
     const float x = Xe[i];
     xfin = xfin && isfinite(x);
     S.X[a * dp + j] = x;
   }
+  }
   for (int i = tid; i < k; i += WG) {
     S.yb[i] = yg[(size_t)e * k + i];
     S.fb[i] = fg[(size_t)e * k + i];
   }
+  if constexpr (!WIDE) {
   for (int j = tid; j < d; j += WG) {
     float s = scale[j];
     S.s2[j] = s * s;
     if (EV) S.betav[j] = s;
+  }
+  } else if constexpr (EV) {
+    for (int j = tid; j < d; j += WG) S.betav[j] = scale[j];
   }
   if (tid == 0) {
     *S.bad = 0;
@@ -365,13 +400,17 @@ fused_laplace_kernel(const float* __restrict__ Xg,   // [E, k, d]
   // multiplies that 0 by the inf — a NaN gradient under bad = 0.  The
   // barrier behind the cache build publishes the flag; the Newton loop and
   // the tail are skipped and f is left alone.
+  // WIDE: the whole cache build, one streamed pass over X that also finds
+  // the non-finite features (t1 carries the row norms)
+  if constexpr (WIDE)
+    xfin = lapw_kb_cache(S.A, SA, S.slab, S.t1, Xe, scale, k, d, tid);
   if (!xfin) *S.bad = 2;
 
   // ---- Kb cache into A's STRICT UPPER (kb = exp(-q); kb_aa = 1) ----
   // Single-buffer design (round 2): the old separate full-K buffer cost
   // a second k x SA region and held the whole kernel at 1 WG/CU; with
   // the expert-NLL upper-cache idiom the kernel fits 2 WGs/CU.
-  {
+  if constexpr (!WIDE) {
     const int nlow = k * (k + 1) / 2;
     for (int f = tid; f < nlow; f += WG) {
       int a, b;
@@ -568,7 +607,8 @@ fused_laplace_kernel(const float* __restrict__ Xg,   // [E, k, d]
       S.pi[i] = -(2.f * p - 1.f) * p * p * __expf(-S.fb[i]);
       S.t2[i] = 0.f;
     }
-    for (int j = tid; j < d + 2; j += WG) S.gout[j] = 0.0;
+    // (WIDE: the beta slots are assigned, not accumulated, by the chunk loop)
+    for (int j = tid; j < (WIDE ? 2 : d + 2); j += WG) S.gout[j] = 0.0;
     __syncthreads();
     // diagKRK_i = || V (sqw o K_:,i) ||^2  (V lower in A; K symmetric).
     // K rows come from the upper cache through a staged 8-row block in T
@@ -591,6 +631,15 @@ fused_laplace_kernel(const float* __restrict__ Xg,   // [E, k, d]
         atomicAdd(&S.t2[i0 + il], z * z);
       }
       __syncthreads();
+    }
+    // WIDE: X comes through the slab buffers, 16 columns (two chunks) at a
+    // time.  Slab 0 goes in here; inside the loops slab s + 1 is loaded at
+    // the top of slab s's first chunk and stored at that chunk's end.
+    [[maybe_unused]] float pre[LAPW_PER];
+    [[maybe_unused]] double* og = out_grad + (size_t)e * (d + 2);
+    if constexpr (WIDE) {
+      lapw_load(Xe, k, d, 0, tid, pre);
+      lapw_store(S.slab, k, tid, pre);
     }
     // s2 vector (K_ii = amp + noise); then u0 = K v - nu v into t2
     for (int i = tid; i < k; i += WG)
@@ -624,12 +673,15 @@ fused_laplace_kernel(const float* __restrict__ Xg,   // [E, k, d]
     float* qb = S.T + 24 * k;
     for (int j0 = 0; j0 < d + 2; j0 += 8) {
       const int cl = min(8, d + 2 - j0);
+      const bool pf = WIDE && j0 % LAPW_SW == 0 && j0 + LAPW_SW < d;
+      if constexpr (WIDE)
+        if (pf) lapw_load(Xe, k, d, j0 / LAPW_SW + 1, tid, pre);
       for (int f = tid; f < k * 8; f += WG) {
         const int a = f >> 3, cc = f & 7;
         const int j = j0 + cc;
         float x = 0.f, w1 = 0.f, w2 = 0.f;
         if (cc < cl && j < d) {
-          x = S.X[(size_t)a * dp + j];
+          x = lap_x<WIDE>(S, k, dp, a, j);
           w1 = x * S.vv[a];
           w2 = x * x * S.vv[a];
         }
@@ -748,9 +800,18 @@ fused_laplace_kernel(const float* __restrict__ Xg,   // [E, k, d]
           for (int a = lane; a < k; a += 64)
             g += (double)S.s2v[a] * (double)wk2[a * 8 + ww];
           g = wave_sum(g);
-          if (lane == 0) S.gout[j0 + ww] += g;
+          if constexpr (!WIDE) {
+            if (lane == 0) S.gout[j0 + ww] += g;
+          } else if (lane == 0) {
+            // this lane is column j's only writer, here and in the s1 loop
+            const int j = j0 + ww;
+            if (j < d) og[j] = g; else S.gout[j - d] += g;
+          }
         }
       }
+      // the other buffer was last read at the top of slab s - 1's chunks
+      if constexpr (WIDE)
+        if (pf) lapw_store(lapw_buf(S.slab, k, j0 / LAPW_SW + 1), k, tid, pre);
       __syncthreads();
     }
 
@@ -820,8 +881,13 @@ fused_laplace_kernel(const float* __restrict__ Xg,   // [E, k, d]
     const double aKba = block_sum(aKba_p, S.red, tid);
     const double a2 = block_sum(a2_p, S.red, tid);
     if (tid == 0) {
-      S.gout[d] += 0.5 * aKba - 0.5 * sRKb;        // s1 for amp
-      S.gout[d + 1] += 0.5 * a2 - 0.5 * trR;       // s1 for noise
+      double* ga = S.gout + (WIDE ? 0 : d);
+      ga[0] += 0.5 * aKba - 0.5 * sRKb;            // s1 for amp
+      ga[1] += 0.5 * a2 - 0.5 * trR;               // s1 for noise
+    }
+    if constexpr (WIDE) {                          // slab 0 again
+      lapw_load(Xe, k, d, 0, tid, pre);
+      lapw_store(S.slab, k, tid, pre);
     }
     // r_a = row sums of W0 into t1
     for (int a = tid; a < k; a += WG) {
@@ -838,9 +904,12 @@ fused_laplace_kernel(const float* __restrict__ Xg,   // [E, k, d]
     // s1 for beta: per 8-col X chunks: WX = W0 X; s1_j = -b_j C (2t1-2t2)
     for (int d0 = 0; d0 < d; d0 += 8) {
       const int cl = min(8, d - d0);
+      const bool pf = WIDE && d0 % LAPW_SW == 0 && d0 + LAPW_SW < d;
+      if constexpr (WIDE)
+        if (pf) lapw_load(Xe, k, d, d0 / LAPW_SW + 1, tid, pre);
       for (int f = tid; f < k * 8; f += WG) {
         const int a = f >> 3, cc = f & 7;
-        qb[f] = (cc < cl) ? S.X[(size_t)a * dp + d0 + cc] : 0.f;
+        qb[f] = (cc < cl) ? lap_x<WIDE>(S, k, dp, a, d0 + cc) : 0.f;
       }
       __syncthreads();
       for (int f = tid; f < k * 8; f += WG) {
@@ -859,9 +928,12 @@ fused_laplace_kernel(const float* __restrict__ Xg,   // [E, k, d]
           }
           g = wave_sum(g);
           if (lane == 0)
-            S.gout[d0 + ww] += -(double)S.betav[d0 + ww] * (double)amp * g;
+            (WIDE ? og : S.gout)[d0 + ww] +=
+                -(double)S.betav[d0 + ww] * (double)amp * g;
         }
       }
+      if constexpr (WIDE)
+        if (pf) lapw_store(lapw_buf(S.slab, k, d0 / LAPW_SW + 1), k, tid, pre);
       __syncthreads();
     }
   }
@@ -870,8 +942,16 @@ fused_laplace_kernel(const float* __restrict__ Xg,   // [E, k, d]
   for (int i = tid; i < k; i += WG) fg[(size_t)e * k + i] = S.fb[i];
   if (EV) {
     if (tid == 0) out_logz[e] = logZ;
+    if constexpr (!WIDE) {
     for (int j = tid; j < d + 2; j += WG)
       out_grad[(size_t)e * (d + 2) + j] = (*S.bad) ? 0.0 : S.gout[j];
+    } else {
+      // the beta entries are in place unless the tail never ran
+      for (int j = tid; j < d + 2; j += WG) {
+        if (*S.bad) out_grad[(size_t)e * (d + 2) + j] = 0.0;
+        else if (j >= d) out_grad[(size_t)e * (d + 2) + j] = S.gout[j - d];
+      }
+    }
   }
   if (tid == 0) {
     out_bad[e] = *S.bad;
@@ -886,7 +966,9 @@ typedef void (*lap_kernel_t)(
     const float*, const float*, float*, const float*, float, float, int, int,
     double, int, double*, double*, int*, int*, double*, double*);
 
-#ifndef LAP_LAUNCHERS
+#ifdef LAP_WIDE
+// laplace_wide.hip goes on with its own launchers
+#elif !defined(LAP_LAUNCHERS)
 
 // a Matern translation unit: hand its two instantiations to the launchers
 extern "C" const void* LAP_KERNEL_GETTER(int ev) {

@@ -60,6 +60,23 @@ hipError_t launch_fused_laplace_evidence(
     double* out_psi, double* out_sumlogl, int* out_iters, int* out_bad,
     double* out_logz, double* out_grad, int family, hipStream_t stream);
 
+// ---- laplace_wide.hip -----------------------------------------------------
+// The two above for the RBF family with X streamed: 1 <= k <= 128 and
+// 1 <= d <= 1024 (lapw_supported); hipErrorInvalidConfiguration otherwise.
+hipError_t launch_fused_laplace_newton_wide(
+    const float* X, const float* y, float* f, const float* scale, float amp,
+    float noise, int E, int k, int d, double tol, int max_newton,
+    double* out_psi, double* out_sumlogl, int* out_iters, int* out_bad,
+    hipStream_t stream);
+
+hipError_t launch_fused_laplace_evidence_wide(
+    const float* X, const float* y, float* f, const float* scale, float amp,
+    float noise, int E, int k, int d, double tol, int max_newton,
+    double* out_psi, double* out_sumlogl, int* out_iters, int* out_bad,
+    double* out_logz, double* out_grad, hipStream_t stream);
+
+hipError_t fused_laplace_wide_resident_wgs(int k, int d, int* out);
+
 // ---- cross_syrk.hip -------------------------------------------------------
 hipError_t launch_cross_kernel_tile(
     const float* X, const float* A, const float* s2v, float amp, int c,

@@ -142,6 +142,14 @@ def supports_laplace(cs: CompiledKernel, X: torch.Tensor,
                             BASES if matern else RBF_BASES)
 
 
+def supports_laplace_wide(cs: CompiledKernel, X: torch.Tensor) -> bool:
+    """Contiguous fp32 experts of an RBF base with k <= 128 rows and up to
+    1024 feature dimensions: what laplace_wide.hip takes (both modes; the
+    kernel streams X, so d is not bound by k)."""
+    return (_supports_expert(cs, X, ext.fused_laplace_wide_supported,
+                             RBF_BASES) and X.is_contiguous())
+
+
 def _fused_laplace(entry, cs: CompiledKernel, theta: np.ndarray,
                    X: torch.Tensor, y: torch.Tensor, f: torch.Tensor,
                    tol: float, max_newton: int):
@@ -164,13 +172,16 @@ def _fused_laplace(entry, cs: CompiledKernel, theta: np.ndarray,
 
 def laplace_newton(cs: CompiledKernel, theta: np.ndarray, X: torch.Tensor,
                    y: torch.Tensor, f: torch.Tensor, tol: float,
-                   max_newton: int) -> int:
+                   max_newton: int, wide: bool = False) -> int:
     """Run the fused per-expert Newton loop to convergence, updating the
     latent ``f`` IN PLACE.  Returns the number of experts the fp32 kernel
     could not handle (their f is left unchanged; the torch evidence pass
-    converges them from their warm state)."""
-    psi, sll, iters, bad = _fused_laplace(ext.fused_laplace_newton, cs, theta,
-                                          X, y, f, tol, max_newton)
+    converges them from their warm state).  ``wide``: launch the
+    streamed-feature kernel (``supports_laplace_wide``)."""
+    entry = (ext.fused_laplace_newton_wide if wide
+             else ext.fused_laplace_newton)
+    psi, sll, iters, bad = _fused_laplace(entry, cs, theta, X, y, f, tol,
+                                          max_newton)
     return int((bad != 0).sum())
 
 
@@ -182,15 +193,18 @@ def supports_laplace_evidence(cs: CompiledKernel, X: torch.Tensor,
 
 def laplace_evidence(cs: CompiledKernel, theta: np.ndarray, X: torch.Tensor,
                      y: torch.Tensor, f: torch.Tensor, tol: float,
-                     max_newton: int):
+                     max_newton: int, wide: bool = False):
     """Fully fused K10+K11: Newton to convergence AND the Algorithm 5.1
     evidence/gradient in one launch (laplace.hip evidence tail).  Updates
     f in place.  Returns (nll, grad) with the torch-path sign convention,
     or None when any expert's fp32 factor broke down (caller falls back
-    to the warm torch Newton)."""
+    to the warm torch Newton).  ``wide``: launch the streamed-feature
+    kernel (``supports_laplace_wide``)."""
     d = X.shape[-1]
-    logz, grad, iters, bad = _fused_laplace(ext.fused_laplace_evidence, cs,
-                                            theta, X, y, f, tol, max_newton)
+    entry = (ext.fused_laplace_evidence_wide if wide
+             else ext.fused_laplace_evidence)
+    logz, grad, iters, bad = _fused_laplace(entry, cs, theta, X, y, f, tol,
+                                            max_newton)
     # one device->host transfer for everything
     stats = torch.cat([logz.sum().reshape(1), bad.sum().double().reshape(1),
                        grad.sum(0)]).cpu().numpy()
