@@ -34,8 +34,12 @@ def main(argv=None):
     p.add_argument("--device", type=str, default=None)
     p.add_argument("--fused-wide-features", action="store_true",
                    help="setFusedWideFeatures(True): the 784-dim experts take "
-                        "the streamed-feature HIP Laplace kernels.  Logistic "
-                        "link only; under --link probit it does nothing")
+                        "the streamed-feature HIP Laplace kernels.  Under "
+                        "--link probit it needs --fused-probit as well")
+    p.add_argument("--fused-probit", action="store_true",
+                   help="setFusedProbit(True): the probit link takes the "
+                        "fused HIP Laplace kernels (here, at d = 784 > k, "
+                        "together with --fused-wide-features)")
     args = p.parse_args(argv)
 
     X, y = mnist_like_binary(args.rows, seed=13)
@@ -50,7 +54,8 @@ def main(argv=None):
           .setTol(1e-3)
           .setMaxIter(args.max_iter)
           .setSeed(13)
-          .setFusedWideFeatures(args.fused_wide_features))
+          .setFusedWideFeatures(args.fused_wide_features)
+          .setFusedProbit(args.fused_probit))
     if args.device:
         gp.setDevice(args.device)
 
@@ -59,7 +64,8 @@ def main(argv=None):
                                  metric=accuracy, seed=13)
     dt = time.perf_counter() - t0
     print(f"rows={args.rows} d=784 m={args.active_set} link={args.link} "
-          f"fused_wide={args.fused_wide_features} accuracy: {acc:.4f}  fit+eval: {dt:.2f}s")
+          f"fused_wide={args.fused_wide_features} "
+          f"fused_probit={args.fused_probit} accuracy: {acc:.4f}  fit+eval: {dt:.2f}s")
     return acc
 
 

@@ -31,6 +31,8 @@ ext = CUDAExtension(
         "spark_gp_amd/ops/csrc/laplace_m32.hip",
         "spark_gp_amd/ops/csrc/laplace_m52.hip",
         "spark_gp_amd/ops/csrc/laplace_wide.hip",
+        "spark_gp_amd/ops/csrc/laplace_probit.hip",
+        "spark_gp_amd/ops/csrc/laplace_wide_probit.hip",
         "spark_gp_amd/ops/csrc/predict.hip",
         "spark_gp_amd/ops/csrc/predict_wide.hip",
         "spark_gp_amd/ops/csrc/greedy.hip",

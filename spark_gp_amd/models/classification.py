@@ -27,13 +27,15 @@ class GaussianProcessClassifier(GaussianProcessCommons):
                    max_newton_iter="_max_newton_iter",
                    link="_link",
                    fused_matern="_fused_matern",
-                   fused_wide_features="_fused_wide_features")
+                   fused_wide_features="_fused_wide_features",
+                   fused_probit="_fused_probit")
 
     def __init__(self, **params):
         self._max_newton_iter = 200
         self._link = "logistic"
         self._fused_matern = False
         self._fused_wide_features = False
+        self._fused_probit = False
         super().__init__(**params)
 
     def setMaxNewtonIter(self, v: int):
@@ -62,10 +64,21 @@ class GaussianProcessClassifier(GaussianProcessCommons):
         """Opt in to the streamed-feature fused HIP Laplace kernels for
         experts with more feature dimensions than rows (d > k, up to 1024
         dimensions and 128 rows; 'rbf' and 'ard' bases under the logistic
-        link).  Default False: those shapes take the batched torch Newton
+        link, and under the probit link with ``setFusedProbit(True)``).
+        Default False: those shapes take the batched torch Newton
         loop, as before; shapes with d <= k take the resident fused kernels
         either way."""
         self._fused_wide_features = bool(v)
+        return self
+
+    def setFusedProbit(self, v: bool):
+        """Opt in to the probit instantiations of the fused HIP Laplace
+        kernels under ``setLink("probit")`` ('rbf' and 'ard' bases; the
+        resident kernels for d <= k, and with ``setFusedWideFeatures(True)``
+        the streamed-feature ones for d > k).  Default False: the probit
+        link takes the batched torch Newton loop, as before.  Nothing
+        changes under the logistic link."""
+        self._fused_probit = bool(v)
         return self
 
     def _resolve_likelihood(self):
@@ -99,7 +112,8 @@ class GaussianProcessClassifier(GaussianProcessCommons):
                     kernel, theta, Xg, yg, fg, self._tol,
                     self._max_newton_iter, likelihood=lik,
                     fused_matern=self._fused_matern,
-                    fused_wide=self._fused_wide_features)
+                    fused_wide=self._fused_wide_features,
+                    fused_probit=self._fused_probit)
                 nll_total += nll
                 grad_total += grad
             return nll_total, grad_total

@@ -96,62 +96,78 @@ def nll_grad_generic(kernel: Kernel, theta: np.ndarray,
 def laplace_nll_grad(kernel: Kernel, theta: np.ndarray, X: torch.Tensor,
                      y: torch.Tensor, f: torch.Tensor, tol: float,
                      max_newton_iter: int = 200, likelihood=None,
-                     fused_matern: bool = False, fused_wide: bool = False):
+                     fused_matern: bool = False, fused_wide: bool = False,
+                     fused_probit: bool = False):
     """``fused_matern``: let the Matern 3/2 and 5/2 bases take the fused HIP
     Laplace kernels as well (opt-in; the RBF bases always do).
     ``fused_wide``: let RBF-base experts with more feature dimensions than
     rows (up to 1024) take the streamed-feature HIP kernels (opt-in; without
-    it those shapes run the batched torch path)."""
+    it those shapes run the batched torch path).
+    ``fused_probit``: let a ``ProbitLikelihood`` on an RBF base take the
+    fused HIP kernels' probit instantiations, through the branches the
+    logistic link takes (opt-in; without it, and for every other
+    likelihood, a non-logistic call runs the batched torch path)."""
     from ..kernels.compiled import compile_kernel
-    from ..likelihoods import LogisticLikelihood
+    from ..likelihoods import LogisticLikelihood, ProbitLikelihood
     logistic = likelihood is None or isinstance(likelihood,
                                                 LogisticLikelihood)
-    # the fused HIP Newton kernel implements the logistic link on compiled
-    # kernels; everything else runs on the batched torch path
-    cs = compile_kernel(kernel) if X.is_cuda and logistic else None
+    probit = fused_probit and isinstance(likelihood, ProbitLikelihood)
+    # the fused HIP Newton kernel implements the logistic link, and the
+    # probit link on request, on compiled kernels; everything else runs on
+    # the batched torch path
+    cs = compile_kernel(kernel) if X.is_cuda and (logistic or probit) \
+        else None
     hip = _backend_for("laplace_nll_grad", X) if cs is not None else None
+    if probit and hip is not None and \
+            not hip.supports_laplace_link(cs, "probit", fused_matern):
+        hip = None
+    # a probit call names its link to the kernels and its likelihood to every
+    # torch pass behind them; a logistic call is the call it always was
+    link = {"link": "probit"} if probit else {}
+    lik = {"likelihood": likelihood} if probit else {}
     if hip is not None:
         if tol >= hip.LAPLACE_MIN_TOL and \
                 hip.supports_laplace_evidence(cs, X, fused_matern):
             # fully fused K10+K11: Newton AND the Algorithm 5.1 evidence
             # in one launch; None -> fp32 breakdown, warm torch fallback
             res = hip.laplace_evidence(cs, theta, X, y, f, tol,
-                                       max_newton_iter)
+                                       max_newton_iter, **link)
             if res is not None:
                 return res
             return torch_backend.laplace_nll_grad(
-                kernel, theta, X, y, f, tol, max_newton_iter)
+                kernel, theta, X, y, f, tol, max_newton_iter, **lik)
         if hip.supports_laplace(cs, X, fused_matern):
             # fused Newton loop runs each expert to convergence on the GPU
             # (updates f in place); the torch pass below then converges in
             # 2-3 cheap iterations and computes the Algorithm 5.1 evidence
             # with the reference's exact semantics.
             n_bad = hip.laplace_newton(cs, theta, X, y, f, tol,
-                                       max_newton_iter)
+                                       max_newton_iter, **link)
             if n_bad == 0 and tol >= hip.LAPLACE_MIN_TOL:
                 # Algorithm 5.1 at the converged f via the contraction
                 # form — no [E, p, k, k] derivative tensor
                 return torch_backend.laplace_evidence_compiled(
-                    cs, theta, X, y, f)
+                    cs, theta, X, y, f, **lik)
             # Some experts fell back, or the user asked for a tol tighter
             # than the fp32 kernel's clamp (LAPLACE_MIN_TOL): the torch
             # Newton polish continues from the warm f with the exact
             # requested tolerance (a few cheap iterations).
             return torch_backend.laplace_nll_grad(
-                kernel, theta, X, y, f, tol, max_newton_iter)
+                kernel, theta, X, y, f, tol, max_newton_iter, **lik)
         if fused_wide and hip.supports_laplace_wide(cs, X):
             # the two branches above on laplace_wide.hip, which streams X
             # (d > k, up to 1024 dimensions)
             if tol >= hip.LAPLACE_MIN_TOL:
                 res = hip.laplace_evidence(cs, theta, X, y, f, tol,
-                                           max_newton_iter, wide=True)
+                                           max_newton_iter, wide=True,
+                                           **link)
                 if res is not None:
                     return res
             else:
                 hip.laplace_newton(cs, theta, X, y, f, tol, max_newton_iter,
-                                   wide=True)
+                                   wide=True, **link)
             return torch_backend.laplace_nll_grad(
-                kernel, theta, X, y, f, tol, max_newton_iter)
+                kernel, theta, X, y, f, tol, max_newton_iter, **lik)
     return torch_backend.laplace_nll_grad(kernel, theta, X, y, f, tol,
                                           max_newton_iter,
                                           likelihood=likelihood)

@@ -590,6 +590,12 @@ void colsum_gemv_acc(torch::Tensor Kc, torch::Tensor y, torch::Tensor Ky) {
             "colsum_gemv");
 }
 
+// the response link code of a fused Laplace entry point (kernel_geom.h)
+void check_link(int64_t link) {
+  TORCH_CHECK(lap_link_ok(link), "link must be 0 (logistic) or 1 (probit), "
+              "got ", link);
+}
+
 // The per-expert Laplace Newton loop, run in place on f.
 // EV = false: returns (psi[E] f64, sumlogl[E] f64, iters[E] i32, bad[E] i32).
 // EV = true: fused Newton + Algorithm 5.1 evidence/gradient (K11) — the
@@ -601,13 +607,20 @@ void colsum_gemv_acc(torch::Tensor Kc, torch::Tensor y, torch::Tensor Ky) {
 // grad) at the given latent, converged or not — the exit state is recomputed
 // at f, nothing is carried over from an iteration.
 // family: the covariance family of the base kernel (default RBF).
+// link: the response link (default logistic); probit is built for the RBF
+// family only.
 template <bool EV>
 std::vector<torch::Tensor> fused_laplace(torch::Tensor X, torch::Tensor y,
                                          torch::Tensor f, torch::Tensor scale,
                                          double amp, double noise, double tol,
-                                         int64_t max_newton, int64_t family) {
+                                         int64_t max_newton, int64_t family,
+                                         int64_t link) {
   const char* what = EV ? "fused_laplace_evidence" : "fused_laplace_newton";
   check_family(family);
+  check_link(link);
+  TORCH_CHECK(link == LAP_LINK_LOGISTIC || family == GEOM_FAM_RBF,
+              "the probit link takes the RBF family only, got family ",
+              family, " for ", what);
   check_arg(X, "X", F32, {ANY, ANY, ANY});
   const int E = X.size(0), k = X.size(1), d = X.size(2);
   check_arg(y, "y", F32, {E, k});
@@ -626,7 +639,7 @@ std::vector<torch::Tensor> fused_laplace(torch::Tensor X, torch::Tensor y,
                   (float)noise, E, k, d, tol, (int)max_newton,
                   psi.data_ptr<double>(), sll.data_ptr<double>(),
                   iters.data_ptr<int>(), bad.data_ptr<int>(), (int)family,
-                  current_stream()),
+                  (int)link, current_stream()),
               what);
     return {psi, sll, iters, bad};
   }
@@ -639,7 +652,7 @@ std::vector<torch::Tensor> fused_laplace(torch::Tensor X, torch::Tensor y,
                 psi.data_ptr<double>(), sll.data_ptr<double>(),
                 iters.data_ptr<int>(), bad.data_ptr<int>(),
                 logz.data_ptr<double>(), grad.data_ptr<double>(),
-                (int)family, current_stream()),
+                (int)family, (int)link, current_stream()),
             what);
   return {logz, grad, iters, bad};
 }
@@ -674,9 +687,10 @@ int64_t fused_laplace_wide_occupancy(int64_t k, int64_t d) {
 template <bool EV>
 std::vector<torch::Tensor> fused_laplace_wide(
     torch::Tensor X, torch::Tensor y, torch::Tensor f, torch::Tensor scale,
-    double amp, double noise, double tol, int64_t max_newton) {
+    double amp, double noise, double tol, int64_t max_newton, int64_t link) {
   const char* what =
       EV ? "fused_laplace_evidence_wide" : "fused_laplace_newton_wide";
+  check_link(link);
   check_arg(X, "X", F32, {ANY, ANY, ANY}, true);
   const int E = X.size(0), k = X.size(1), d = X.size(2);
   check_arg(y, "y", F32, {E, k});
@@ -695,7 +709,7 @@ std::vector<torch::Tensor> fused_laplace_wide(
                   f.data_ptr<float>(), scale.data_ptr<float>(), (float)amp,
                   (float)noise, E, k, d, tol, (int)max_newton,
                   psi.data_ptr<double>(), sll.data_ptr<double>(),
-                  iters.data_ptr<int>(), bad.data_ptr<int>(),
+                  iters.data_ptr<int>(), bad.data_ptr<int>(), (int)link,
                   current_stream()),
               what);
     return {psi, sll, iters, bad};
@@ -708,7 +722,7 @@ std::vector<torch::Tensor> fused_laplace_wide(
                 (float)noise, E, k, d, tol, (int)max_newton,
                 psi.data_ptr<double>(), sll.data_ptr<double>(),
                 iters.data_ptr<int>(), bad.data_ptr<int>(),
-                logz.data_ptr<double>(), grad.data_ptr<double>(),
+                logz.data_ptr<double>(), grad.data_ptr<double>(), (int)link,
                 current_stream()),
             what);
   return {logz, grad, iters, bad};
@@ -1098,6 +1112,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.attr("FAM_RBF") = (int)GEOM_FAM_RBF;
   mod.attr("FAM_M32") = (int)GEOM_FAM_M32;
   mod.attr("FAM_M52") = (int)GEOM_FAM_M52;
+  // response link codes of the `link` arguments of the fused Laplace entries
+  mod.attr("LINK_LOGISTIC") = (int)LAP_LINK_LOGISTIC;
+  mod.attr("LINK_PROBIT") = (int)LAP_LINK_PROBIT;
   mod.def("synth_regression", &synth_regression,
           "device-side Philox benchmark data (K19)");
   mod.def("dpotrf64", &dpotrf64,
@@ -1111,23 +1128,27 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
           "per-expert Laplace Newton loop to convergence (CDNA4)",
           pybind11::arg("X"), pybind11::arg("y"), pybind11::arg("f"), pybind11::arg("scale"), pybind11::arg("amp"),
           pybind11::arg("noise"), pybind11::arg("tol"), pybind11::arg("max_newton"),
-          pybind11::arg("family") = (int)GEOM_FAM_RBF);
+          pybind11::arg("family") = (int)GEOM_FAM_RBF,
+          pybind11::arg("link") = (int)LAP_LINK_LOGISTIC);
   mod.def("fused_laplace_newton_supported", &fused_laplace_newton_supported);
   mod.def("fused_laplace_evidence", &fused_laplace<true>,
           "fused Newton + Algorithm 5.1 evidence/gradient (K11, CDNA4)",
           pybind11::arg("X"), pybind11::arg("y"), pybind11::arg("f"), pybind11::arg("scale"), pybind11::arg("amp"),
           pybind11::arg("noise"), pybind11::arg("tol"), pybind11::arg("max_newton"),
-          pybind11::arg("family") = (int)GEOM_FAM_RBF);
+          pybind11::arg("family") = (int)GEOM_FAM_RBF,
+          pybind11::arg("link") = (int)LAP_LINK_LOGISTIC);
   mod.def("fused_laplace_evidence_supported",
           &fused_laplace_evidence_supported);
   mod.def("fused_laplace_newton_wide", &fused_laplace_wide<false>,
           "fused_laplace_newton with X streamed: d up to 1024, d > k allowed",
           pybind11::arg("X"), pybind11::arg("y"), pybind11::arg("f"), pybind11::arg("scale"), pybind11::arg("amp"),
-          pybind11::arg("noise"), pybind11::arg("tol"), pybind11::arg("max_newton"));
+          pybind11::arg("noise"), pybind11::arg("tol"), pybind11::arg("max_newton"),
+          pybind11::arg("link") = (int)LAP_LINK_LOGISTIC);
   mod.def("fused_laplace_evidence_wide", &fused_laplace_wide<true>,
           "fused_laplace_evidence with X streamed: d up to 1024, d > k allowed",
           pybind11::arg("X"), pybind11::arg("y"), pybind11::arg("f"), pybind11::arg("scale"), pybind11::arg("amp"),
-          pybind11::arg("noise"), pybind11::arg("tol"), pybind11::arg("max_newton"));
+          pybind11::arg("noise"), pybind11::arg("tol"), pybind11::arg("max_newton"),
+          pybind11::arg("link") = (int)LAP_LINK_LOGISTIC);
   mod.def("fused_laplace_wide_supported", &fused_laplace_wide_supported);
   mod.def("fused_laplace_wide_occupancy", &fused_laplace_wide_occupancy);
   mod.def("fused_expert_nll", &fused_expert_nll,

@@ -29,6 +29,14 @@ static inline bool geom_family_ok(long family) {
   return family >= GEOM_FAM_RBF && family <= GEOM_FAM_M52;
 }
 
+// ---- response links of the fused Laplace kernels (laplace_link.h) ---------
+#define LAP_LINK_LOGISTIC 0
+#define LAP_LINK_PROBIT 1
+
+static inline bool lap_link_ok(long link) {
+  return link == LAP_LINK_LOGISTIC || link == LAP_LINK_PROBIT;
+}
+
 #ifdef __HIPCC__
 // Kb at a q that may carry a small negative rounding residue
 template <int FAM>

@@ -41,6 +41,15 @@
 // column slabs (laplace_wide.h) for the Kb cache, built on the fp32 matrix
 // cores, and for the two feature loops of the evidence tail.  Every
 // difference sits behind `if constexpr (WIDE)`.
+//
+// Response links: fused_laplace_kernel<EV, FAM, WIDE, LINK>.  The likelihood
+// enters at five elementwise places — the head of a Newton iteration (w, sqw,
+// b), the log-likelihood of the candidate objective, the exit-state
+// recompute of the tail (v = dlogp, b), the log-likelihood of the tail's psi,
+// and d3 = dW/df — and laplace_link.h has what each link puts there.  The
+// probit instantiations (RBF family, resident and WIDE) are compiled in
+// laplace_probit.hip and laplace_wide_probit.hip; they share every LDS region
+// and plan with the logistic ones (pi carries d3 from the recompute on).
 
 //
 // Covariance families: the kernel is fused_laplace_kernel<EV, FAM>, compiled
@@ -86,6 +95,11 @@
 
 #include "linalg_lds.h"
 #include "laplace_wide.h"
+#include "laplace_link.h"
+
+#ifndef LAP_LINK
+#define LAP_LINK LAP_LINK_LOGISTIC
+#endif
 
 struct LapLds {
   float* X;     // k * dp4: raw features (16-B-aligned rows); not WIDE
@@ -96,7 +110,7 @@ struct LapLds {
   float* T;     // max(k*36, 32*SA, 448) scratch for the chol machinery
   float* yb;    // k
   float* fb;    // k   latent
-  float* pi;    // k
+  float* pi;    // k   logistic: pi; probit: d3 (from the exit-state recompute)
   float* sqw;   // k
   float* bv;    // k   b = w f + (y - pi)
   float* av;    // k   a
@@ -104,7 +118,7 @@ struct LapLds {
   float* t2;    // k
   float* s2;    // d; not WIDE
   // evidence-mode (EV) extras
-  float* vv;    // k   v = y - pi
+  float* vv;    // k   v = dlogp (logistic: y - pi)
   float* s2v;   // k   Algorithm 5.1 s2 vector
   float* betav; // d   raw base scale (beta), signed
   double* gout; // d+2 gradient accumulators (beta..., amp, noise); WIDE:
@@ -333,13 +347,7 @@ __device__ __forceinline__ float lap_x(const LapLds& S, const int k,
     return lapw_buf(S.slab, k, j / LAPW_SW)[a * LAPW_SS + j % LAPW_SW];
 }
 
-__device__ inline double log_sigmoid(double v) {
-  // log(1/(1+exp(-v))) = -log1p(exp(-v)), stable for both signs
-  if (v < -30.0) return v;
-  return -log1p(exp(-v));
-}
-
-template <bool EV, int FAM, bool WIDE = false>
+template <bool EV, int FAM, bool WIDE = false, int LINK = LAP_LINK_LOGISTIC>
 __global__ void __launch_bounds__(WG, 4)   // 4 waves/SIMD = 2 WGs/CU
 fused_laplace_kernel(const float* __restrict__ Xg,   // [E, k, d]
                      const float* __restrict__ yg,   // [E, k]
@@ -357,6 +365,8 @@ fused_laplace_kernel(const float* __restrict__ Xg,   // [E, k, d]
   // the strict upper triangle caches t = sqrt(q), not Kb (header comment)
   constexpr bool TC = EV && FAM != GEOM_FAM_RBF;
   static_assert(!WIDE || FAM == GEOM_FAM_RBF, "the streamed form is RBF's");
+  static_assert(LINK == LAP_LINK_LOGISTIC || FAM == GEOM_FAM_RBF,
+                "the probit link is built for the RBF family only");
   extern __shared__ char lds_raw[];
   const int SA = (int)geom_sa(k);
   LapLds S = lap_carve<EV, WIDE>(lds_raw, k, d);
@@ -454,6 +464,7 @@ fused_laplace_kernel(const float* __restrict__ Xg,   // [E, k, d]
   const int nmax = *S.bad ? 0 : max_newton;   // block-uniform
   for (; it < nmax; ++it) {
     // pi, w, sqw, b
+    if constexpr (LINK == LAP_LINK_LOGISTIC) {
     for (int i = tid; i < k; i += WG) {
       const float fi = S.fb[i];
       const float p = 1.f / (1.f + __expf(-fi));
@@ -461,6 +472,15 @@ fused_laplace_kernel(const float* __restrict__ Xg,   // [E, k, d]
       S.pi[i] = p;
       S.sqw[i] = sqrtf(w);
       S.bv[i] = w * fi + (S.yb[i] - p);
+    }
+    } else {
+      // probit: sqw and b alone (the loop reads nothing else of the link)
+      for (int i = tid; i < k; i += WG) {
+        float w, dl, b, d3;
+        probit_terms<false>(S.fb[i], S.yb[i], w, dl, b, d3);
+        S.sqw[i] = sqrtf(w);
+        S.bv[i] = b;
+      }
     }
     if (tid == 0) S.misc[0] = 0.0;
     __syncthreads();
@@ -515,7 +535,7 @@ fused_laplace_kernel(const float* __restrict__ Xg,   // [E, k, d]
       const float fc = (1.f - sf) * S.fb[i] + sf * S.t1[i];
       S.t2[i] = fc;
       part += -0.5 * (double)S.av[i] * (double)fc
-              + log_sigmoid((double)((2.f * S.yb[i] - 1.f) * fc));
+              + lap_log_lik<LINK>((double)((2.f * S.yb[i] - 1.f) * fc));
     }
     const double obj_cand = block_sum(part, S.red, tid);
     if (obj_cand > old_obj) {
@@ -539,6 +559,7 @@ fused_laplace_kernel(const float* __restrict__ Xg,   // [E, k, d]
   double logZ = 0.0;
   if (EV && !*S.bad) {
     // exit-state recompute at the converged f
+    if constexpr (LINK == LAP_LINK_LOGISTIC) {
     for (int i = tid; i < k; i += WG) {
       const float fi = S.fb[i];
       const float p = 1.f / (1.f + __expf(-fi));
@@ -547,6 +568,18 @@ fused_laplace_kernel(const float* __restrict__ Xg,   // [E, k, d]
       S.sqw[i] = sqrtf(w);
       S.vv[i] = S.yb[i] - p;
       S.bv[i] = w * fi + S.vv[i];
+    }
+    } else {
+      // probit: pi carries d3 = dW/df from here, from the same evaluation of
+      // h (nothing reads pi before the d3 step below)
+      for (int i = tid; i < k; i += WG) {
+        float w, dl, b, d3;
+        probit_terms<true>(S.fb[i], S.yb[i], w, dl, b, d3);
+        S.pi[i] = d3;
+        S.sqw[i] = sqrtf(w);
+        S.vv[i] = dl;
+        S.bv[i] = b;
+      }
     }
     if (tid == 0) S.misc[0] = 0.0;
     __syncthreads();
@@ -589,22 +622,24 @@ fused_laplace_kernel(const float* __restrict__ Xg,   // [E, k, d]
       for (int i = tid; i < k; i += WG) {
         const float fc = lap_kdot(S.A, SA, k, i, S.av, amp, noise);
         part += -0.5 * (double)S.av[i] * (double)fc
-                + log_sigmoid((double)((2.f * S.yb[i] - 1.f) * fc));
+                + lap_log_lik<LINK>((double)((2.f * S.yb[i] - 1.f) * fc));
       }
     } else {
       const float fc = lap_kdot_t<FAM>(S.A, SA, k, tid, S.av, amp, noise);
       const int i = tid / LAP_NL;
       if (tid % LAP_NL == 0 && i < k)
         part = -0.5 * (double)S.av[i] * (double)fc
-               + log_sigmoid((double)((2.f * S.yb[i] - 1.f) * fc));
+               + lap_log_lik<LINK>((double)((2.f * S.yb[i] - 1.f) * fc));
     }
     const double psi = block_sum(part, S.red, tid);
     logZ = psi - 0.5 * S.misc[0];
 
     // d3 into pi; zero diagKRK accumulators (t2) and gout
     for (int i = tid; i < k; i += WG) {
+      if constexpr (LINK == LAP_LINK_LOGISTIC) {
       const float p = S.pi[i];
       S.pi[i] = -(2.f * p - 1.f) * p * p * __expf(-S.fb[i]);
+      }                                   // probit: d3 is there already
       S.t2[i] = 0.f;
     }
     // (WIDE: the beta slots are assigned, not accumulated, by the chunk loop)
@@ -970,19 +1005,27 @@ typedef void (*lap_kernel_t)(
 // laplace_wide.hip goes on with its own launchers
 #elif !defined(LAP_LAUNCHERS)
 
-// a Matern translation unit: hand its two instantiations to the launchers
+// a Matern or probit translation unit: hand its two instantiations to the
+// launchers
 extern "C" const void* LAP_KERNEL_GETTER(int ev) {
-  return ev ? (const void*)fused_laplace_kernel<true, LAP_FAMILY>
-            : (const void*)fused_laplace_kernel<false, LAP_FAMILY>;
+  return ev
+      ? (const void*)fused_laplace_kernel<true, LAP_FAMILY, false, LAP_LINK>
+      : (const void*)fused_laplace_kernel<false, LAP_FAMILY, false, LAP_LINK>;
 }
 
 #else   // the RBF translation unit: the launchers of every family
 
 extern "C" const void* lap_kernel_m32(int ev);   // laplace_m32.hip
 extern "C" const void* lap_kernel_m52(int ev);   // laplace_m52.hip
+extern "C" const void* lap_kernel_probit(int ev);   // laplace_probit.hip
 
-// the instantiation of a family code; null for an unknown one
-static lap_kernel_t lap_kernel_of(int family, int ev) {
+// the instantiation of a family and a link code; null for an unknown one, and
+// for a Matern family under the probit link, which is not built
+static lap_kernel_t lap_kernel_of(int family, int link, int ev) {
+  if (link == LAP_LINK_PROBIT)
+    return family == GEOM_FAM_RBF ? (lap_kernel_t)lap_kernel_probit(ev)
+                                  : nullptr;
+  if (link != LAP_LINK_LOGISTIC) return nullptr;
   switch (family) {
     case GEOM_FAM_RBF:
       return ev ? fused_laplace_kernel<true, GEOM_FAM_RBF>
@@ -997,8 +1040,8 @@ extern "C" hipError_t launch_fused_laplace_newton(
     const float* X, const float* y, float* f, const float* scale, float amp,
     float noise, int E, int k, int d, double tol, int max_newton,
     double* out_psi, double* out_sumlogl, int* out_iters, int* out_bad,
-    int family, hipStream_t stream) {
-  const lap_kernel_t kern = lap_kernel_of(family, 0);
+    int family, int link, hipStream_t stream) {
+  const lap_kernel_t kern = lap_kernel_of(family, link, 0);
   size_t lds = lap_lds_bytes(k, d);
   if (!kern || lds > GEOM_LDS_MAX || k > 128 || d > k)
     return hipErrorInvalidConfiguration;
@@ -1013,8 +1056,9 @@ extern "C" hipError_t launch_fused_laplace_evidence(
     const float* X, const float* y, float* f, const float* scale, float amp,
     float noise, int E, int k, int d, double tol, int max_newton,
     double* out_psi, double* out_sumlogl, int* out_iters, int* out_bad,
-    double* out_logz, double* out_grad, int family, hipStream_t stream) {
-  const lap_kernel_t kern = lap_kernel_of(family, 1);
+    double* out_logz, double* out_grad, int family, int link,
+    hipStream_t stream) {
+  const lap_kernel_t kern = lap_kernel_of(family, link, 1);
   size_t lds = lap_lds_bytes(k, d, 1);
   if (!kern || lds > GEOM_LDS_MAX || k > 128 || d > k)
     return hipErrorInvalidConfiguration;

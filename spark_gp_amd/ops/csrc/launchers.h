@@ -46,34 +46,37 @@ hipError_t launch_fused_expert_nll_f64(
     int family, hipStream_t stream);
 
 // ---- laplace.hip ----------------------------------------------------------
-// (these two answer an unknown family, like an unsupported (k, d), with
-// hipErrorInvalidConfiguration)
+// `link`: a LAP_LINK_* code of kernel_geom.h.  (These two answer an unknown
+// family or link, and a Matern family under the probit link, like an
+// unsupported (k, d): with hipErrorInvalidConfiguration.)
 hipError_t launch_fused_laplace_newton(
     const float* X, const float* y, float* f, const float* scale, float amp,
     float noise, int E, int k, int d, double tol, int max_newton,
     double* out_psi, double* out_sumlogl, int* out_iters, int* out_bad,
-    int family, hipStream_t stream);
+    int family, int link, hipStream_t stream);
 
 hipError_t launch_fused_laplace_evidence(
     const float* X, const float* y, float* f, const float* scale, float amp,
     float noise, int E, int k, int d, double tol, int max_newton,
     double* out_psi, double* out_sumlogl, int* out_iters, int* out_bad,
-    double* out_logz, double* out_grad, int family, hipStream_t stream);
+    double* out_logz, double* out_grad, int family, int link,
+    hipStream_t stream);
 
 // ---- laplace_wide.hip -----------------------------------------------------
 // The two above for the RBF family with X streamed: 1 <= k <= 128 and
-// 1 <= d <= 1024 (lapw_supported); hipErrorInvalidConfiguration otherwise.
+// 1 <= d <= 1024 (lapw_supported); hipErrorInvalidConfiguration otherwise,
+// and for an unknown link.
 hipError_t launch_fused_laplace_newton_wide(
     const float* X, const float* y, float* f, const float* scale, float amp,
     float noise, int E, int k, int d, double tol, int max_newton,
     double* out_psi, double* out_sumlogl, int* out_iters, int* out_bad,
-    hipStream_t stream);
+    int link, hipStream_t stream);
 
 hipError_t launch_fused_laplace_evidence_wide(
     const float* X, const float* y, float* f, const float* scale, float amp,
     float noise, int E, int k, int d, double tol, int max_newton,
     double* out_psi, double* out_sumlogl, int* out_iters, int* out_bad,
-    double* out_logz, double* out_grad, hipStream_t stream);
+    double* out_logz, double* out_grad, int link, hipStream_t stream);
 
 hipError_t fused_laplace_wide_resident_wgs(int k, int d, int* out);
 

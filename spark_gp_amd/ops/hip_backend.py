@@ -150,9 +150,24 @@ def supports_laplace_wide(cs: CompiledKernel, X: torch.Tensor) -> bool:
                              RBF_BASES) and X.is_contiguous())
 
 
+LINKS = {"logistic": ext.LINK_LOGISTIC, "probit": ext.LINK_PROBIT}
+
+
+def supports_laplace_link(cs: CompiledKernel, link: str,
+                          matern: bool = False) -> bool:
+    """Whether the fused Laplace kernels are built for ``link`` on the base
+    of ``cs``: logistic on every family (the Matern ones under ``matern``, as
+    ``supports_laplace`` has it), probit on the RBF bases only.  The shape
+    gates (``supports_laplace*``) are the same for both links."""
+    if cs is None or link not in LINKS:
+        return False
+    return cs.base in (RBF_BASES if link == "probit" or not matern
+                       else BASES)
+
+
 def _fused_laplace(entry, cs: CompiledKernel, theta: np.ndarray,
                    X: torch.Tensor, y: torch.Tensor, f: torch.Tensor,
-                   tol: float, max_newton: int):
+                   tol: float, max_newton: int, link: str = "logistic"):
     """Call one of the two fused Laplace entry points; ``f`` is updated IN
     PLACE.  The fused loop is a warm-starter: a torch pass finishes
     convergence with reference semantics where needed, so the fp32
@@ -165,6 +180,8 @@ def _fused_laplace(entry, cs: CompiledKernel, theta: np.ndarray,
     # an RBF call is the call it always was; only the Matern families name
     # theirs
     kw = {"family": fam} if fam != FAM_RBF else {}
+    if link != "logistic":
+        kw["link"] = LINKS[link]
     return entry(X, y.to(torch.float32), f, scale, float(cs.amp(theta)),
                  float(cs.noise(theta)), max(float(tol), LAPLACE_MIN_TOL),
                  min(int(max_newton), 40), **kw)
@@ -172,16 +189,18 @@ def _fused_laplace(entry, cs: CompiledKernel, theta: np.ndarray,
 
 def laplace_newton(cs: CompiledKernel, theta: np.ndarray, X: torch.Tensor,
                    y: torch.Tensor, f: torch.Tensor, tol: float,
-                   max_newton: int, wide: bool = False) -> int:
+                   max_newton: int, wide: bool = False,
+                   link: str = "logistic") -> int:
     """Run the fused per-expert Newton loop to convergence, updating the
     latent ``f`` IN PLACE.  Returns the number of experts the fp32 kernel
     could not handle (their f is left unchanged; the torch evidence pass
     converges them from their warm state).  ``wide``: launch the
-    streamed-feature kernel (``supports_laplace_wide``)."""
+    streamed-feature kernel (``supports_laplace_wide``).  ``link``:
+    "logistic" or "probit" (``supports_laplace_link``)."""
     entry = (ext.fused_laplace_newton_wide if wide
              else ext.fused_laplace_newton)
     psi, sll, iters, bad = _fused_laplace(entry, cs, theta, X, y, f, tol,
-                                          max_newton)
+                                          max_newton, link)
     return int((bad != 0).sum())
 
 
@@ -193,18 +212,20 @@ def supports_laplace_evidence(cs: CompiledKernel, X: torch.Tensor,
 
 def laplace_evidence(cs: CompiledKernel, theta: np.ndarray, X: torch.Tensor,
                      y: torch.Tensor, f: torch.Tensor, tol: float,
-                     max_newton: int, wide: bool = False):
+                     max_newton: int, wide: bool = False,
+                     link: str = "logistic"):
     """Fully fused K10+K11: Newton to convergence AND the Algorithm 5.1
     evidence/gradient in one launch (laplace.hip evidence tail).  Updates
     f in place.  Returns (nll, grad) with the torch-path sign convention,
     or None when any expert's fp32 factor broke down (caller falls back
     to the warm torch Newton).  ``wide``: launch the streamed-feature
-    kernel (``supports_laplace_wide``)."""
+    kernel (``supports_laplace_wide``).  ``link``: "logistic" or "probit"
+    (``supports_laplace_link``)."""
     d = X.shape[-1]
     entry = (ext.fused_laplace_evidence_wide if wide
              else ext.fused_laplace_evidence)
     logz, grad, iters, bad = _fused_laplace(entry, cs, theta, X, y, f, tol,
-                                            max_newton)
+                                            max_newton, link)
     # one device->host transfer for everything
     stats = torch.cat([logz.sum().reshape(1), bad.sum().double().reshape(1),
                        grad.sum(0)]).cpu().numpy()

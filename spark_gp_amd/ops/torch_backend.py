@@ -303,7 +303,7 @@ def kmn_knm_and_kmny(kernel: Kernel, active: torch.Tensor,
 
 def laplace_evidence_experts(cs: CompiledKernel, theta: np.ndarray,
                              X: torch.Tensor, y: torch.Tensor,
-                             f: torch.Tensor
+                             f: torch.Tensor, likelihood=None
                              ) -> Tuple[torch.Tensor, torch.Tensor]:
     """Per-expert Algorithm 5.1 evidence and gradient at an already-converged
     latent f: (logZ [E], g [E, d + 2]) in fp64, g the gradient of logZ over
@@ -315,7 +315,11 @@ def laplace_evidence_experts(cs: CompiledKernel, theta: np.ndarray,
     C*Kb(q) + nu*I, dK/ds_j = -2 s_j C Kd o (x_j - x'_j)^2, so the dK_j
     contractions reduce to batched GEMMs via the regression path's identities
     with G := a a^T - R, and the dK_j matvecs (s3) via
-    (dK_j v) = -2 s_j (C Kd) @ [v, X o v, X^2 o v] recombined."""
+    (dK_j v) = -2 s_j (C Kd) @ [v, X o v, X^2 o v] recombined.
+
+    ``likelihood``: None runs the logistic expressions below as written; a
+    ``Likelihood`` gives w, d1, d3 and log_lik instead, all at ``f`` (the
+    exit-state convention of the fused kernels: f_eval == f_final)."""
     C = cs.amp(theta)
     nu = cs.noise(theta)
     Kb, Kd, s = _base_matrices(cs, theta, X)
@@ -327,25 +331,34 @@ def laplace_evidence_experts(cs: CompiledKernel, theta: np.ndarray,
     K = C * Kb + nu * eyek
 
     # exit-state quantities of Algorithm 3.1 at f
-    pi = torch.sigmoid(f)
-    w = pi * (1.0 - pi)
+    if likelihood is None:
+        pi = torch.sigmoid(f)
+        w = pi * (1.0 - pi)
+        v = y - pi                               # grad log p
+    else:
+        w = likelihood.w(f, y)
+        v = likelihood.d1(f, y)
     sqw = torch.sqrt(w)
     B = eyek + sqw.unsqueeze(-1) * K * sqw.unsqueeze(-2)
     L = torch.linalg.cholesky(B)
-    v = y - pi                                   # grad log p
     b = w * f + v
     Kb_vec = (K @ b.unsqueeze(-1)).squeeze(-1)
     t = torch.cholesky_solve((sqw * Kb_vec).unsqueeze(-1), L).squeeze(-1)
     a = b - sqw * t
     fc = (K @ a.unsqueeze(-1)).squeeze(-1)
-    psi = (-0.5 * (a * fc).sum(-1).double()
-           + torch.nn.functional.logsigmoid((2.0 * y - 1.0) * fc)
-           .double().sum(-1))
+    if likelihood is None:
+        log_lik = torch.nn.functional.logsigmoid((2.0 * y - 1.0) * fc)
+    else:
+        log_lik = likelihood.log_lik(fc, y)
+    psi = -0.5 * (a * fc).sum(-1).double() + log_lik.double().sum(-1)
     logZ = psi - torch.log(L.diagonal(dim1=-2, dim2=-1)).double().sum(-1)
 
     R = sqw.unsqueeze(-1) * torch.cholesky_solve(torch.diag_embed(sqw), L)
     KR = K @ R
-    d3 = -(2.0 * pi - 1.0) * pi * pi * torch.exp(-f)
+    if likelihood is None:
+        d3 = -(2.0 * pi - 1.0) * pi * pi * torch.exp(-f)
+    else:
+        d3 = likelihood.d3(f, y)
     # (K R K)_ii = sum_j (KR)_ij K_ji = (KR o K).sum(-1) since K is
     # symmetric — avoids materializing the full [E, k, k] product
     diagKRK = (KR * K).sum(-1)
@@ -380,10 +393,12 @@ def laplace_evidence_experts(cs: CompiledKernel, theta: np.ndarray,
 
 def laplace_evidence_compiled(cs: CompiledKernel, theta: np.ndarray,
                               X: torch.Tensor, y: torch.Tensor,
-                              f: torch.Tensor) -> Tuple[float, np.ndarray]:
+                              f: torch.Tensor, likelihood=None
+                              ) -> Tuple[float, np.ndarray]:
     """Negative Laplace evidence summed over the expert batch and its
-    gradient over theta, at an already-converged latent f."""
-    logZ, g = laplace_evidence_experts(cs, theta, X, y, f)
+    gradient over theta, at an already-converged latent f (``likelihood``
+    as ``laplace_evidence_experts`` takes it)."""
+    logZ, g = laplace_evidence_experts(cs, theta, X, y, f, likelihood)
     d = X.shape[-1]
     g = g.sum(0).cpu().numpy()
     grad = cs.assemble_grad(theta, g[:d], float(g[d]), float(g[d + 1]))
